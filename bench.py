@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py - structures/s of the PeSTo forward pass (i_v4_1 architecture) on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W   -> ONE JSON line on rank 0.
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   -> ONE JSON line on rank 0.
+  * a plain run does only what the headline needs: set-up, clock pre-roll, W warm-up steps, the K timed steps, the outputs of the
+    last timed step (--dump-outputs), the line (metric, value, unit, higher_is_better, dtype, ms_per_step = ms of one timed step).
+    Every side measurement and check below (roofline, whole_forward, long_sample, segment_call, batch1 latency, exact fp32, the
+    config-4 legs, the CPU baseline, the parity check against the reference golden, per-rank times) runs with --full only; without
+    it their keys are null;
+  * --dump-outputs DIR: after the timed steps, the logits z [sum R, 5] of the last timed step as DIR/z.npy (float32; rank r > 0 of a
+    multi-rank run: DIR/z_rank<r>.npy; with --mode strong also the gathered config-4 logits as DIR/config4_z.npy). The inputs are
+    seeded: the same arguments give the same inputs in every run;
   * one "step" = one call of the reference's own signature, Model.forward(X, ids_topk, q, M), over one collated batch of --batch
     synthetic structures (N=3000 atoms, k=64, R=375 each; BASELINE.json configs[1]) with every input - the dense fp32 mask M
     included - already resident in HBM (the mask is reduced to residue segments on the GPU inside the call);
@@ -124,8 +132,12 @@ def per_nn_table(config, kern, n1, traffic_file):
 
 
 def make_batch(n_atoms, batch, seed0, n0, order="random"):
+    from concurrent.futures import ThreadPoolExecutor
     from pesto_amd.topology import collate_batch_features, mask_to_segments, synthetic_structure
-    items = [list(synthetic_structure(n_atoms, seed0 + b, n0=n0, order=order)) for b in range(batch)]
+    # the structures are independent and seeded: built on a few threads (the dense host topology's numpy sort releases the GIL), the
+    # same arrays as one after the other - set-up time outside the timed steps
+    with ThreadPoolExecutor(max_workers=max(1, min(batch, 8))) as ex:
+        items = list(ex.map(lambda b: list(synthetic_structure(n_atoms, seed0 + b, n0=n0, order=order)), range(batch)))
     X, ids, q, M = collate_batch_features(items)
     roa, R = mask_to_segments(M)
     return X, ids, q, roa, R
@@ -303,11 +315,12 @@ def config4_structures(n_structures, model=None, forms="compact"):
     return [tuple(it) for it in items], sizes, refs
 
 
-def config4_leg(model, dist, backend, dev, n_structures, reps, max_atoms, forms="compact", fixed_list=False):
+def config4_leg(model, dist, backend, dev, n_structures, reps, max_atoms, forms="compact", fixed_list=False, outputs=None):
     """The config-4 work list sharded by pesto_amd.sharding (LPT partition, per-rank launches of <= max_atoms atoms from host memory,
     ragged all_gather of the logits). fixed_list=False: n_structures grows with the world size (weak); True: the SAME list at every world
     size (SURVEY 8e's acceptance: >= 7x on 8 GPUs for a list of >= 64 structures), with a world-1 pass of the list on rank 0 timed beside
-    it (`speedup_vs_world1`). Returns the leg's result dict on rank 0."""
+    it (`speedup_vs_world1`). Returns the leg's result dict on rank 0; with a dict `outputs`, rank 0 also puts the gathered logits of the
+    last timed pass there (key "config4_z": the structures' logits concatenated in list order)."""
     import torch
     from pesto_amd import sharding
     structures, sizes, refs = config4_structures(n_structures, model, forms)
@@ -354,6 +367,8 @@ def config4_leg(model, dist, backend, dev, n_structures, reps, max_atoms, forms=
         barrier()
     if rank != 0:
         return None
+    if outputs is not None:
+        outputs["config4_z"] = np.concatenate([np.asarray(g, dtype=np.float32) for g in gathered])
     # world-1 run of the same list on this rank; every structure must come back with the same bits (PESTO_BATCH_INDEPENDENT)
     local = sharding.forward_local(model, structures, list(range(len(structures))), max_atoms=max_atoms)
     ok = all(g is not None and np.array_equal(g, local[i]) for i, g in enumerate(gathered))
@@ -385,6 +400,14 @@ def config4_leg(model, dist, backend, dev, n_structures, reps, max_atoms, forms=
             "rank_local_s_max_over_min": float(max(np.median([p[r][0] for p in per_rank]) for r in range(world)) /
                                                max(1e-12, min(np.median([p[r][0] for p in per_rank]) for r in range(world)))),
             "host_cpu_s_per_structure": float(np.median([sum(p[r][2] for r in range(world)) for p in per_rank]) / len(structures))}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array (torch tensor or numpy) as <out_dir>/<name>.npy in float32 (float64 stays float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def gather_rank_stats(dist, backend, dev, values):
@@ -432,10 +455,16 @@ def main():
     ap.add_argument("--mode", default="weak", choices=["weak", "strong"],
                     help="headline value: weak = config 2 replicated per rank; strong = the config-4 work list sharded over the ranks")
     ap.add_argument("--precision", default="auto", choices=["auto", "f16_split", "fp32"], help="pesto_precision of the timed steps")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU-baseline work (0 = skip)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (roofline, whole forward, 200-step sample, segment call, batch-1 "
+                         "latency, exact fp32, config-4 legs, CPU baseline, parity against the reference golden); a plain run times "
+                         "the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step as DIR/z.npy (float32) after the timed steps")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of CPU-baseline work (0 = skip)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the batch-1 latency side measurement")
     ap.add_argument("--no-check", action="store_true", help="developer ablation builds only: do not check the timed output")
-    ap.add_argument("--no-extras", action="store_true", help="skip the exact-fp32 and config-4 legs (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the exact-fp32 and config-4 legs (profiling runs)")
     ap.add_argument("--config4-structures", type=int, default=64, help="structures PER RANK of the config-4 leg (the list has this many x world size)")
     ap.add_argument("--config4-max-atoms", type=int, default=24576, help="atoms per collated launch of the config-4 legs (sharding.forward_sharded)")
     ap.add_argument("--strong-structures", type=int, default=512, help="size of the FIXED list of the config4_strong leg (N > 1 only)")
@@ -598,275 +627,280 @@ def run(args, stage):
             torch.cuda.synchronize()
             preroll_steps += 1
     elapsed, z = timed(args.warmup, args.steps)
-    rank_times = timed_per_rank(args.steps) if world > 1 else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"z" if rank == 0 else f"z_rank{rank}": z})
+    rank_times = timed_per_rank(args.steps) if world > 1 and args.full else None
     assert args.no_check or torch.isfinite(z).all()
     status = model.status()
 
-    # ---- the timed output against the reference: structure 0 of rank 0 is the committed golden (seed 1, N=3000, i_v4_1 stacked)
-    parity = None
-    gpath = os.path.join(ROOT, "tests", "golden", "fwd_i_v4_1_stacked_synth3000.npz")
-    if rank == 0 and args.config == "i_v4_1" and args.atoms == 3000 and args.order == "random" and os.path.exists(gpath) and not args.no_check:
-        zg = np.load(gpath)["z"]
-        parity = float(np.abs(z[:zg.shape[0]].cpu().numpy() - zg).max())
-        assert parity < 1e-4, f"timed output differs from the reference golden by {parity}"
+    # everything below up to the result line is a side measurement or check: --full only (a plain run times the headline steps)
+    parity = exact = roofline = whole = long_sample = seg_call = lat_ms = lat_detail = None
+    if args.full:
+        # ---- the timed output against the reference: structure 0 of rank 0 is the committed golden (seed 1, N=3000, i_v4_1 stacked)
+        gpath = os.path.join(ROOT, "tests", "golden", "fwd_i_v4_1_stacked_synth3000.npz")
+        if rank == 0 and args.config == "i_v4_1" and args.atoms == 3000 and args.order == "random" and os.path.exists(gpath) and not args.no_check:
+            zg = np.load(gpath)["z"]
+            parity = float(np.abs(z[:zg.shape[0]].cpu().numpy() - zg).max())
+            assert parity < 1e-4, f"timed output differs from the reference golden by {parity}"
 
-    # ---- the same step on the exact fp32 MFMA kernels (what "auto" falls back to)
-    exact = None
-    if not args.no_extras and args.precision != "fp32":
-        model.set_precision("fp32")
-        el32, z32 = timed(2, max(3, min(args.steps, 10)))
-        model.set_precision(args.precision)
-        exact = {"value": max(3, min(args.steps, 10)) * args.batch * world / el32,
-                 "max_abs_vs_timed_output": float((z32 - z).abs().max().item())}
-        # per-kernel launch times of the exact path (HIP events between consecutive launches) against the fp32 MFMA peak
-        model.set_precision("fp32")
+        # ---- the same step on the exact fp32 MFMA kernels (what "auto" falls back to)
+        if not args.no_extras and args.precision != "fp32":
+            model.set_precision("fp32")
+            el32, z32 = timed(2, max(3, min(args.steps, 10)))
+            model.set_precision(args.precision)
+            exact = {"value": max(3, min(args.steps, 10)) * args.batch * world / el32,
+                     "max_abs_vs_timed_output": float((z32 - z).abs().max().item())}
+            # per-kernel launch times of the exact path (HIP events between consecutive launches) against the fp32 MFMA peak
+            model.set_precision("fp32")
+            model.set_timing(True, per_kernel=True)
+            pk32 = []
+            for _ in range(3):
+                step_segments()
+                torch.cuda.synchronize()
+                pk32.append(model.get_kernel_timing())
+            model.set_timing(False)
+            model.set_precision(args.precision)
+            n1_ = X.shape[0] + 1
+            ex_k = {}
+            for name in pk32[0]:
+                n_l = pk32[0][name][1]
+                if not n_l:
+                    continue
+                ms_ = float(np.median([pk[name][0] for pk in pk32])) / n_l
+                fl_ = EXACT_NODE_MFMA_FLOPS_PER_ATOM * n1_ * (len(config["sum"]) / n_l) if name == "node" else exact_edge_mfma_flops_per_atom(int(name[7:])) * n1_
+                ex_k[name] = {"launches_per_forward": n_l, "avg_launch_ms": ms_, "executed_mfma_TFLOPs": fl_ / (ms_ * 1e-3) / 1e12,
+                              "frac_of_fp32_mfma_peak": fl_ / (ms_ * 1e-3) / 1e12 / PEAK_F32_TFLOPS}
+            fl_all = sum(exact_edge_mfma_flops_per_atom(l["nn"]) + EXACT_NODE_MFMA_FLOPS_PER_ATOM for l in config["sum"]) * n1_
+            t_all32 = sum(v["avg_launch_ms"] * v["launches_per_forward"] for v in ex_k.values()) * 1e-3
+            exact["kernels"] = ex_k
+            exact["frac_of_fp32_mfma_peak"] = fl_all / t_all32 / 1e12 / PEAK_F32_TFLOPS if t_all32 > 0 else None
+            exact["peak_TFLOPs"] = PEAK_F32_TFLOPS
+            exact["definition"] = ("FLOPs the matrix cores execute in k_edge<..., F16 = false> (layers 2 / 3 of the edge MLPs and the centre terms; the "
+                                   "neighbour terms of layer 1 are VALU work there) and k_node, / time by HIP events / the 157.3 TF fp32 MFMA peak")
+
+        # ---- roofline leg: HIP events around the state-update launches, on the stream they run on
+        # (each sample = the LAST of three back-to-back steps: its events are recorded into a busy stream, as in the timed region of the headline;
+        #  a step that starts on a drained GPU reads ~1 % longer)
+        model.set_timing(True)
+        lay_ms = []
+        for _ in range(max(5, min(args.steps, 20))):
+            for _ in range(3):
+                step()
+            torch.cuda.synchronize()
+            lay_ms.append(model.get_timing())
+        # per-kernel pass (one event between consecutive layer launches): average launch duration of every kernel class
         model.set_timing(True, per_kernel=True)
-        pk32 = []
-        for _ in range(3):
-            step_segments()
+        per_kernel = []
+        for _ in range(5):
+            for _ in range(3):
+                step()
             torch.cuda.synchronize()
-            pk32.append(model.get_kernel_timing())
+            per_kernel.append(model.get_kernel_timing())
         model.set_timing(False)
-        model.set_precision(args.precision)
-        n1_ = X.shape[0] + 1
-        ex_k = {}
-        for name in pk32[0]:
-            n_l = pk32[0][name][1]
-            if not n_l:
-                continue
-            ms_ = float(np.median([pk[name][0] for pk in pk32])) / n_l
-            fl_ = EXACT_NODE_MFMA_FLOPS_PER_ATOM * n1_ * (len(config["sum"]) / n_l) if name == "node" else exact_edge_mfma_flops_per_atom(int(name[7:])) * n1_
-            ex_k[name] = {"launches_per_forward": n_l, "avg_launch_ms": ms_, "executed_mfma_TFLOPs": fl_ / (ms_ * 1e-3) / 1e12,
-                          "frac_of_fp32_mfma_peak": fl_ / (ms_ * 1e-3) / 1e12 / PEAK_F32_TFLOPS}
-        fl_all = sum(exact_edge_mfma_flops_per_atom(l["nn"]) + EXACT_NODE_MFMA_FLOPS_PER_ATOM for l in config["sum"]) * n1_
-        t_all32 = sum(v["avg_launch_ms"] * v["launches_per_forward"] for v in ex_k.values()) * 1e-3
-        exact["kernels"] = ex_k
-        exact["frac_of_fp32_mfma_peak"] = fl_all / t_all32 / 1e12 / PEAK_F32_TFLOPS if t_all32 > 0 else None
-        exact["peak_TFLOPs"] = PEAK_F32_TFLOPS
-        exact["definition"] = ("FLOPs the matrix cores execute in k_edge<..., F16 = false> (layers 2 / 3 of the edge MLPs and the centre terms; the "
-                               "neighbour terms of layer 1 are VALU work there) and k_node, / time by HIP events / the 157.3 TF fp32 MFMA peak")
+        kern = {}
+        for name in per_kernel[0]:
+            n_l = per_kernel[0][name][1]
+            if n_l:
+                kern[name] = {"launches_per_forward": n_l, "avg_launch_ms": float(np.median([pk[name][0] for pk in per_kernel])) / n_l}
+        layers_ms = float(np.median([t["layers_ms"] for t in lay_ms]))
+        fwd_all = np.array([t["total_ms"] for t in lay_ms])
+        fwd_ms = float(np.median(fwd_all))
+        n_launch = lay_ms[0]["n_layer_launches"]
+        n1 = n_atoms_total + 1
+        flops = sum(layer_flops_per_atom(l["nn"]) for l in config["sum"]) * n1
+        gbytes = sum(layer_gather_bytes_per_atom(l["nn"]) for l in config["sum"]) * n1
+        # HBM-side bytes from the committed PMC passes of THIS build (profiles/pmc_collect.sh stamps the file with the source hash)
+        traffic_file, traffic_note = None, "no PMC file for this workload"
+        tpath = os.path.join(ROOT, "profiles", f"traffic_{args.config}_n{args.atoms}_b{args.batch}.json")
+        if os.path.exists(tpath) and args.order == "random":
+            tf = json.load(open(tpath))
+            if tf.get("source_hash") == source_hash():
+                traffic_file, traffic_note = tf, f"rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE per dispatch, {os.path.basename(tpath)} (source hash matches this build)"
+            else:
+                traffic_note = f"{os.path.basename(tpath)} was collected on other kernel sources (hash {tf.get('source_hash')} != {source_hash()}): not quoted"
+        # the dominant kernel: k_edge<nn = max>; SURVEY 8d per atom-layer: FLOP 2*(13,696 + 36,376 n), bytes (A) 1,024 + 532 n
+        nn_max = max(l["nn"] for l in config["sum"])
+        dom = kern.get(f"edge_nn{nn_max}")
+        if dom:
+            t_s = dom["avg_launch_ms"] * 1e-3
+            b_a = layer_gather_bytes_per_atom(nn_max) * n1
+            # launches of this kernel that also write the next layer's records (every layer but the last has a successor)
+            n_dom = sum(1 for l in config["sum"] if l["nn"] == nn_max)
+            n_prep = sum(1 for i, l in enumerate(config["sum"]) if l["nn"] == nn_max and i + 1 < len(config["sum"]))
+            f_exec = n1 * (edge_mfma_flops_per_atom(nn_max) + NODE_MFMA_FLOPS_PER_ATOM * n_prep / n_dom)
+            f_ref = 2.0 * 36376.0 * nn_max * n1
+            hbm_frac = b_a / t_s / 1e9 / PEAK_HBM_GBS
+            mfma_frac = f_exec / t_s / 1e12 / PEAK_F16_TFLOPS
+            t_all = sum(v["avg_launch_ms"] * v["launches_per_forward"] for v in kern.values())
+            traffic = None
+            if traffic_file:
+                hit = [v for k, v in traffic_file["kernels"].items() if f"k_edge<{nn_max}," in k]
+                if hit:
+                    traffic = 2.0 * hit[0]["fetch_bytes_per_dispatch_raw"] + hit[0]["write_bytes_per_dispatch"]
+            per_nn, frac_rocprof = per_nn_table(config, kern, n1, traffic_file)
+            dom_row = per_nn.get(str(nn_max), {})
+            hbm_actual = dom_row.get("hbm_actual_frac")
+            # what binds: the matrix pipe or the fabric only when one of them is at least half used. The achieved / peak / frac keys keep SURVEY
+            # 8d's definition (A) - gather-counted bytes against the HBM peak, a cache-bandwidth figure - whatever `bound` says; with neither
+            # pipe half used the kernel is bound by the NUMBER of instructions it issues (issue_floor_ratio prices them)
+            bound = "mfma" if mfma_frac >= 0.5 else ("hbm" if (hbm_actual if hbm_actual is not None else hbm_frac) >= 0.5 else "issue")
+            roofline = {
+                "kernel": f"k_edge<{nn_max}> = one whole state-update layer: edges, attention, the layer's output MLPs (finish phase) and the next "
+                          f"layer's per-atom records (prepare phase) (dominant: {dom['avg_launch_ms'] * dom['launches_per_forward'] / t_all:.0%} of the layer time)",
+                "bound": bound,
+                "bound_note": "issue = instruction issue: the fabric sees hbm_actual_frac of its peak, the matrix cores run at mfma.frac of theirs; "
+                              "achieved / peak / frac are SURVEY 8d's definition (A) (algorithmic gather-counted bytes / launch time / 8 TB/s)",
+                "achieved": f_exec / t_s / 1e12 if bound == "mfma" else b_a / t_s / 1e9,
+                "peak": PEAK_F16_TFLOPS if bound == "mfma" else PEAK_HBM_GBS,
+                "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
+                "frac": mfma_frac if bound == "mfma" else hbm_frac,
+                # traffic / launch time / 8 TB/s: what the fabric actually carried (committed PMC passes of this build)
+                "hbm_actual_frac": hbm_actual,
+                # launch time / (dynamic instruction classes of the launch x the micro-benchmark price list at the clock of the profiled dispatch)
+                "issue_floor_ratio": dom_row.get("issue_floor_ratio"),
+                "clock_GHz": dom_row.get("clock_GHz"),
+                # the same fraction from the COMMITTED rocprofv3 kernel trace (average duration of this kernel in the hash-stamped profile
+                # of this build, profiles/traffic_*.json; the profiler adds ~5 % to a launch and the trace may come from another box of
+                # the pool): null when the committed profile was taken on other kernel sources
+                "frac_rocprof": frac_rocprof.get(nn_max) if bound != "mfma" else None,
+                "traffic": traffic,
+                # SURVEY 8d definition (B): compulsory bytes with a perfect cache - own state read + written (1,024 B) and 4 B of ids per edge
+                "traffic_over_compulsory": (traffic / ((1024.0 + 4.0 * nn_max) * n1)) if traffic else None,
+                "avg_launch_ms": dom["avg_launch_ms"], "atoms_per_launch": n1,
+                "hbm": {"algorithmic_bytes_per_launch": b_a, "achieved_GBps": b_a / t_s / 1e9, "peak_GBps": PEAK_HBM_GBS, "frac": hbm_frac,
+                        "definition": "SURVEY 8d (A): gather-counted bytes, (1,024 + 532 nn) per atom-layer - own state read + written (the "
+                                      "kernel does both) and, per edge, the neighbour's 512 B state, 16 B geometry and 4 B id. The launch is the "
+                                      "whole layer since round 2 (in round 1 a 23-29 us node launch per layer was timed separately and not "
+                                      "counted in this kernel's duration). Most gathers hit L2 / Infinity Cache, so this is a cache-bandwidth figure priced at "
+                                      "the HBM peak; `traffic` is what actually reached the fabric"},
+                "mfma": {"executed_flops_per_launch": f_exec, "achieved_TFLOPs": f_exec / t_s / 1e12, "peak_TFLOPs": PEAK_F16_TFLOPS, "frac": mfma_frac,
+                         "definition": "FLOPs the matrix cores execute (3 products per f16-split GEMM, fp32 accumulate) / dense f16 MFMA peak "
+                                       "(spec 2.5 PF; v_mfma_f32_16x16x32_f16 itself tops out at 2.0-2.1 PF on this chip, "
+                                       "profiles/microbench/r02_peaks.txt)"},
+                "useful_TFLOPs": f_ref / t_s / 1e12,
+                "useful_definition": "reference-formulation FLOPs of the edge part (SURVEY 8d: 2 x 36,376 x nn per atom) / time; the kernel executes "
+                                     "fewer (first-layer linearity) on the f16 pipe, so this is NOT a fraction of any peak",
+                "traffic_note": traffic_note,
+                # every layer kernel, not only the dominant one: the worst fraction is visible in the line
+                "per_nn": per_nn,
+            }
+        whole = {"layers_ms": layers_ms, "forward_ms": fwd_ms, "launches": n_launch,
+                 "forward_ms_p10_p90": [float(np.percentile(fwd_all, 10)), float(np.percentile(fwd_all, 90))],
+                 "hbm_frac_def_A": gbytes / (layers_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "bytes_def_A_per_forward": gbytes,
+                 "executed_mfma_frac_of_f16_peak": executed_mfma_flops(config, n1) / (layers_ms * 1e-3) / 1e12 / PEAK_F16_TFLOPS,
+                 "useful_TFLOPs": flops / (layers_ms * 1e-3) / 1e12,
+                 "hbm_bytes_per_forward_measured": traffic_file.get("hbm_bytes_per_forward") if traffic_file else None,
+                 "kernels": kern}
 
-    # ---- roofline leg: HIP events around the state-update launches, on the stream they run on
-    # (each sample = the LAST of three back-to-back steps: its events are recorded into a busy stream, as in the timed region of the headline;
-    #  a step that starts on a drained GPU reads ~1 % longer)
-    model.set_timing(True)
-    lay_ms = []
-    for _ in range(max(5, min(args.steps, 20))):
-        for _ in range(3):
-            step()
-        torch.cuda.synchronize()
-        lay_ms.append(model.get_timing())
-    # per-kernel pass (one event between consecutive layer launches): average launch duration of every kernel class
-    model.set_timing(True, per_kernel=True)
-    per_kernel = []
-    for _ in range(5):
-        for _ in range(3):
-            step()
-        torch.cuda.synchronize()
-        per_kernel.append(model.get_kernel_timing())
-    model.set_timing(False)
-    kern = {}
-    for name in per_kernel[0]:
-        n_l = per_kernel[0][name][1]
-        if n_l:
-            kern[name] = {"launches_per_forward": n_l, "avg_launch_ms": float(np.median([pk[name][0] for pk in per_kernel])) / n_l}
-    layers_ms = float(np.median([t["layers_ms"] for t in lay_ms]))
-    fwd_all = np.array([t["total_ms"] for t in lay_ms])
-    fwd_ms = float(np.median(fwd_all))
-    n_launch = lay_ms[0]["n_layer_launches"]
-    n1 = n_atoms_total + 1
-    flops = sum(layer_flops_per_atom(l["nn"]) for l in config["sum"]) * n1
-    gbytes = sum(layer_gather_bytes_per_atom(l["nn"]) for l in config["sum"]) * n1
-    # HBM-side bytes from the committed PMC passes of THIS build (profiles/pmc_collect.sh stamps the file with the source hash)
-    traffic_file, traffic_note = None, "no PMC file for this workload"
-    tpath = os.path.join(ROOT, "profiles", f"traffic_{args.config}_n{args.atoms}_b{args.batch}.json")
-    if os.path.exists(tpath) and args.order == "random":
-        tf = json.load(open(tpath))
-        if tf.get("source_hash") == source_hash():
-            traffic_file, traffic_note = tf, f"rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE per dispatch, {os.path.basename(tpath)} (source hash matches this build)"
-        else:
-            traffic_note = f"{os.path.basename(tpath)} was collected on other kernel sources (hash {tf.get('source_hash')} != {source_hash()}): not quoted"
-    # the dominant kernel: k_edge<nn = max>; SURVEY 8d per atom-layer: FLOP 2*(13,696 + 36,376 n), bytes (A) 1,024 + 532 n
-    nn_max = max(l["nn"] for l in config["sum"])
-    dom = kern.get(f"edge_nn{nn_max}")
-    roofline = None
-    if dom:
-        t_s = dom["avg_launch_ms"] * 1e-3
-        b_a = layer_gather_bytes_per_atom(nn_max) * n1
-        # launches of this kernel that also write the next layer's records (every layer but the last has a successor)
-        n_dom = sum(1 for l in config["sum"] if l["nn"] == nn_max)
-        n_prep = sum(1 for i, l in enumerate(config["sum"]) if l["nn"] == nn_max and i + 1 < len(config["sum"]))
-        f_exec = n1 * (edge_mfma_flops_per_atom(nn_max) + NODE_MFMA_FLOPS_PER_ATOM * n_prep / n_dom)
-        f_ref = 2.0 * 36376.0 * nn_max * n1
-        hbm_frac = b_a / t_s / 1e9 / PEAK_HBM_GBS
-        mfma_frac = f_exec / t_s / 1e12 / PEAK_F16_TFLOPS
-        t_all = sum(v["avg_launch_ms"] * v["launches_per_forward"] for v in kern.values())
-        traffic = None
-        if traffic_file:
-            hit = [v for k, v in traffic_file["kernels"].items() if f"k_edge<{nn_max}," in k]
-            if hit:
-                traffic = 2.0 * hit[0]["fetch_bytes_per_dispatch_raw"] + hit[0]["write_bytes_per_dispatch"]
-        per_nn, frac_rocprof = per_nn_table(config, kern, n1, traffic_file)
-        dom_row = per_nn.get(str(nn_max), {})
-        hbm_actual = dom_row.get("hbm_actual_frac")
-        # what binds: the matrix pipe or the fabric only when one of them is at least half used. The achieved / peak / frac keys keep SURVEY
-        # 8d's definition (A) - gather-counted bytes against the HBM peak, a cache-bandwidth figure - whatever `bound` says; with neither
-        # pipe half used the kernel is bound by the NUMBER of instructions it issues (issue_floor_ratio prices them)
-        bound = "mfma" if mfma_frac >= 0.5 else ("hbm" if (hbm_actual if hbm_actual is not None else hbm_frac) >= 0.5 else "issue")
-        roofline = {
-            "kernel": f"k_edge<{nn_max}> = one whole state-update layer: edges, attention, the layer's output MLPs (finish phase) and the next "
-                      f"layer's per-atom records (prepare phase) (dominant: {dom['avg_launch_ms'] * dom['launches_per_forward'] / t_all:.0%} of the layer time)",
-            "bound": bound,
-            "bound_note": "issue = instruction issue: the fabric sees hbm_actual_frac of its peak, the matrix cores run at mfma.frac of theirs; "
-                          "achieved / peak / frac are SURVEY 8d's definition (A) (algorithmic gather-counted bytes / launch time / 8 TB/s)",
-            "achieved": f_exec / t_s / 1e12 if bound == "mfma" else b_a / t_s / 1e9,
-            "peak": PEAK_F16_TFLOPS if bound == "mfma" else PEAK_HBM_GBS,
-            "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
-            "frac": mfma_frac if bound == "mfma" else hbm_frac,
-            # traffic / launch time / 8 TB/s: what the fabric actually carried (committed PMC passes of this build)
-            "hbm_actual_frac": hbm_actual,
-            # launch time / (dynamic instruction classes of the launch x the micro-benchmark price list at the clock of the profiled dispatch)
-            "issue_floor_ratio": dom_row.get("issue_floor_ratio"),
-            "clock_GHz": dom_row.get("clock_GHz"),
-            # the same fraction from the COMMITTED rocprofv3 kernel trace (average duration of this kernel in the hash-stamped profile
-            # of this build, profiles/traffic_*.json; the profiler adds ~5 % to a launch and the trace may come from another box of
-            # the pool): null when the committed profile was taken on other kernel sources
-            "frac_rocprof": frac_rocprof.get(nn_max) if bound != "mfma" else None,
-            "traffic": traffic,
-            # SURVEY 8d definition (B): compulsory bytes with a perfect cache - own state read + written (1,024 B) and 4 B of ids per edge
-            "traffic_over_compulsory": (traffic / ((1024.0 + 4.0 * nn_max) * n1)) if traffic else None,
-            "avg_launch_ms": dom["avg_launch_ms"], "atoms_per_launch": n1,
-            "hbm": {"algorithmic_bytes_per_launch": b_a, "achieved_GBps": b_a / t_s / 1e9, "peak_GBps": PEAK_HBM_GBS, "frac": hbm_frac,
-                    "definition": "SURVEY 8d (A): gather-counted bytes, (1,024 + 532 nn) per atom-layer - own state read + written (the "
-                                  "kernel does both) and, per edge, the neighbour's 512 B state, 16 B geometry and 4 B id. The launch is the "
-                                  "whole layer since round 2 (in round 1 a 23-29 us node launch per layer was timed separately and not "
-                                  "counted in this kernel's duration). Most gathers hit L2 / Infinity Cache, so this is a cache-bandwidth figure priced at "
-                                  "the HBM peak; `traffic` is what actually reached the fabric"},
-            "mfma": {"executed_flops_per_launch": f_exec, "achieved_TFLOPs": f_exec / t_s / 1e12, "peak_TFLOPs": PEAK_F16_TFLOPS, "frac": mfma_frac,
-                     "definition": "FLOPs the matrix cores execute (3 products per f16-split GEMM, fp32 accumulate) / dense f16 MFMA peak "
-                                   "(spec 2.5 PF; v_mfma_f32_16x16x32_f16 itself tops out at 2.0-2.1 PF on this chip, "
-                                   "profiles/microbench/r02_peaks.txt)"},
-            "useful_TFLOPs": f_ref / t_s / 1e12,
-            "useful_definition": "reference-formulation FLOPs of the edge part (SURVEY 8d: 2 x 36,376 x nn per atom) / time; the kernel executes "
-                                 "fewer (first-layer linearity) on the f16 pipe, so this is NOT a fraction of any peak",
-            "traffic_note": traffic_note,
-            # every layer kernel, not only the dominant one: the worst fraction is visible in the line
-            "per_nn": per_nn,
-        }
-    whole = {"layers_ms": layers_ms, "forward_ms": fwd_ms, "launches": n_launch,
-             "forward_ms_p10_p90": [float(np.percentile(fwd_all, 10)), float(np.percentile(fwd_all, 90))],
-             "hbm_frac_def_A": gbytes / (layers_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "bytes_def_A_per_forward": gbytes,
-             "executed_mfma_frac_of_f16_peak": executed_mfma_flops(config, n1) / (layers_ms * 1e-3) / 1e12 / PEAK_F16_TFLOPS,
-             "useful_TFLOPs": flops / (layers_ms * 1e-3) / 1e12,
-             "hbm_bytes_per_forward_measured": traffic_file.get("hbm_bytes_per_forward") if traffic_file else None,
-             "kernels": kern}
+        # ---- side sample: >= 200 consecutive steps, one HIP event pair per step on the launch stream (no host sync in between)
+        if not args.no_extras:
+            n_long = max(200, args.steps)
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_long + 1)]
+            # the clock and the package power THIS box holds under the workload (the stamped roofline.clock_GHz is the profile box's): amdsmi's
+            # current gfx clock / socket power through torch, sampled by a host thread while the 200 steps run (boxes of the pool differ by
+            # several per cent in the clock they hold at the 1,400 W cap - VERDICT r5 weak item 4)
+            import threading
+            live, stop = [], threading.Event()
 
-    # ---- side sample: >= 200 consecutive steps, one HIP event pair per step on the launch stream (no host sync in between)
-    long_sample = None
-    if not args.no_extras:
-        n_long = max(200, args.steps)
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_long + 1)]
-        # the clock and the package power THIS box holds under the workload (the stamped roofline.clock_GHz is the profile box's): amdsmi's
-        # current gfx clock / socket power through torch, sampled by a host thread while the 200 steps run (boxes of the pool differ by
-        # several per cent in the clock they hold at the 1,400 W cap - VERDICT r5 weak item 4)
-        import threading
-        live, stop = [], threading.Event()
-
-        def sampler():
-            while not stop.is_set():
-                try:
-                    live.append((float(torch.cuda.clock_rate(dev)), float(torch.cuda.power_draw(dev))))
-                except Exception:      # noqa: BLE001 - no amdsmi on this host: the keys stay null
-                    return
-                time.sleep(0.004)
-        th = threading.Thread(target=sampler, daemon=True)
-        barrier()
-        th.start()
-        evs[0].record()
-        for i in range(n_long):
-            step()
-            evs[i + 1].record()
-        torch.cuda.synchronize()
-        stop.set()
-        th.join(timeout=2.0)
-        dt = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(n_long)])
-        live_clock = None
-        if len(live) >= 8:
-            lv = np.array(live[len(live) // 4:])      # (the first quarter: the queue is still filling)
-            pw = lv[:, 1] / (1000.0 if np.median(lv[:, 1]) > 5000.0 else 1.0)
-            live_clock = {"sclk_GHz_mean": float(lv[:, 0].mean() / 1e3), "sclk_GHz_min_max": [float(lv[:, 0].min() / 1e3), float(lv[:, 0].max() / 1e3)],
-                          "power_W_mean": float(pw.mean()), "samples": int(len(lv)),
-                          "how": "torch.cuda.clock_rate() / power_draw() (amdsmi) every 4 ms from a host thread during the 200-step sample; the mean "
-                                 "over the forward's kernel mix (k_edge<64> holds less, k_edge<8> more)"}
-        long_sample = {"steps": n_long, "ms_per_step_median": float(np.median(dt)), "ms_per_step_p10": float(np.percentile(dt, 10)),
-                       "ms_per_step_p90": float(np.percentile(dt, 90)), "ms_per_step_mean": float(dt.mean()),
-                       "structures_per_s_from_median": args.batch / float(np.median(dt)) * 1e3, "live_clock": live_clock,
-                       "how": "HIP events between consecutive steps on torch's current stream (the stream the kernels are launched on)"}
-
-    # ---- the same forward with the mask pre-reduced by the caller (forward_segments: res_of_atom instead of M); until round 5 the headline
-    seg_call = None
-    if not args.no_extras:
-        n_sig = max(5, min(args.steps, 20))
-        for _ in range(2):
-            zs = step_segments()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(n_sig):
-            zs = step_segments()
-        torch.cuda.synchronize()
-        t_sig = (time.perf_counter() - t1) / n_sig
-        seg_call = {"call": "Model.forward_segments(X, ids_topk, q, res_of_atom, R): the dense mask reduced by the caller (not in the timed region)",
-                    "mask_bytes_not_read": int(n_atoms_total) * int(R) * 4, "steps": n_sig, "ms_per_step": t_sig * 1e3,
-                    "structures_per_s": args.batch / t_sig, "bitwise_equal_to_the_headline_call": bool(torch.equal(zs, z)),
-                    "step_minus_this_step_ms": elapsed / args.steps * 1e3 - t_sig * 1e3}
-        # the mask pass by itself: HIP events around n_sig reductions of the resident mask on the stream the forward runs on (the difference of
-        # the two timed legs above is smaller than their run-to-run spread)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        model._segments(Md)
-        torch.cuda.synchronize()
-        ev[0].record()
-        for _ in range(n_sig):
-            model._segments(Md)
-        ev[1].record()
-        torch.cuda.synchronize()
-        seg_call["mask_pass_ms_per_step"] = ev[0].elapsed_time(ev[1]) / n_sig
-        seg_call["mask_pass_GBps"] = int(n_atoms_total) * int(R) * 4 / (seg_call["mask_pass_ms_per_step"] * 1e-3) / 1e9
-
-    # ---- side measurement: batch-1 latency (ms per structure when structures arrive one at a time)
-    lat_ms = lat_detail = None
-    if not args.no_latency and args.batch > 1:
-        X1, ids1, q1, roa1, R1 = make_batch(args.atoms, 1, 1000 * rank + 1, n0, args.order)
-        a = [torch.from_numpy(v).to(dev) for v in (X1, ids1, q1, roa1)]
-        def calls(n):
-            t1 = time.perf_counter()
-            for _ in range(n):
-                model.forward_segments(a[0], a[1], a[2], a[3], R1)
+            def sampler():
+                while not stop.is_set():
+                    try:
+                        live.append((float(torch.cuda.clock_rate(dev)), float(torch.cuda.power_draw(dev))))
+                    except Exception:      # noqa: BLE001 - no amdsmi on this host: the keys stay null
+                        return
+                    time.sleep(0.004)
+            th = threading.Thread(target=sampler, daemon=True)
+            barrier()
+            th.start()
+            evs[0].record()
+            for i in range(n_long):
+                step()
+                evs[i + 1].record()
             torch.cuda.synchronize()
-            return (time.perf_counter() - t1) / n * 1e3
-        calls(3)
-        # a burst on an idle GPU: its first ten calls (what rounds 1 - 4 reported as ms_per_structure_batch1: 3 warm-up calls, 10 timed)
-        time.sleep(0.1)
-        lat_cold = calls(10)
-        # steady state of back-to-back calls: the clocks have ramped (about 30 calls, profiles/r05_clock_ramp.txt)
-        calls(30)
-        lat_ms = calls(50)
-        lat_detail = {"steady_state_ms": lat_ms, "calls": 50, "warmup_calls": 43,
-                      "first_10_calls_after_100ms_idle_ms": lat_cold,
-                      "note": "one model.forward_segments call per structure on device tensors, precision as the line; the GPU drops to its idle "
-                              "clocks within tens of ms without work and needs ~30 calls to ramp back (profiles/r05_clock_ramp.txt)"}
+            stop.set()
+            th.join(timeout=2.0)
+            dt = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(n_long)])
+            live_clock = None
+            if len(live) >= 8:
+                lv = np.array(live[len(live) // 4:])      # (the first quarter: the queue is still filling)
+                pw = lv[:, 1] / (1000.0 if np.median(lv[:, 1]) > 5000.0 else 1.0)
+                live_clock = {"sclk_GHz_mean": float(lv[:, 0].mean() / 1e3), "sclk_GHz_min_max": [float(lv[:, 0].min() / 1e3), float(lv[:, 0].max() / 1e3)],
+                              "power_W_mean": float(pw.mean()), "samples": int(len(lv)),
+                              "how": "torch.cuda.clock_rate() / power_draw() (amdsmi) every 4 ms from a host thread during the 200-step sample; the mean "
+                                     "over the forward's kernel mix (k_edge<64> holds less, k_edge<8> more)"}
+            long_sample = {"steps": n_long, "ms_per_step_median": float(np.median(dt)), "ms_per_step_p10": float(np.percentile(dt, 10)),
+                           "ms_per_step_p90": float(np.percentile(dt, 90)), "ms_per_step_mean": float(dt.mean()),
+                           "structures_per_s_from_median": args.batch / float(np.median(dt)) * 1e3, "live_clock": live_clock,
+                           "how": "HIP events between consecutive steps on torch's current stream (the stream the kernels are launched on)"}
+
+        # ---- the same forward with the mask pre-reduced by the caller (forward_segments: res_of_atom instead of M); until round 5 the headline
+        if not args.no_extras:
+            n_sig = max(5, min(args.steps, 20))
+            for _ in range(2):
+                zs = step_segments()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(n_sig):
+                zs = step_segments()
+            torch.cuda.synchronize()
+            t_sig = (time.perf_counter() - t1) / n_sig
+            seg_call = {"call": "Model.forward_segments(X, ids_topk, q, res_of_atom, R): the dense mask reduced by the caller (not in the timed region)",
+                        "mask_bytes_not_read": int(n_atoms_total) * int(R) * 4, "steps": n_sig, "ms_per_step": t_sig * 1e3,
+                        "structures_per_s": args.batch / t_sig, "bitwise_equal_to_the_headline_call": bool(torch.equal(zs, z)),
+                        "step_minus_this_step_ms": elapsed / args.steps * 1e3 - t_sig * 1e3}
+            # the mask pass by itself: HIP events around n_sig reductions of the resident mask on the stream the forward runs on (the difference of
+            # the two timed legs above is smaller than their run-to-run spread)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            model._segments(Md)
+            torch.cuda.synchronize()
+            ev[0].record()
+            for _ in range(n_sig):
+                model._segments(Md)
+            ev[1].record()
+            torch.cuda.synchronize()
+            seg_call["mask_pass_ms_per_step"] = ev[0].elapsed_time(ev[1]) / n_sig
+            seg_call["mask_pass_GBps"] = int(n_atoms_total) * int(R) * 4 / (seg_call["mask_pass_ms_per_step"] * 1e-3) / 1e9
+
+        # ---- side measurement: batch-1 latency (ms per structure when structures arrive one at a time)
+        if not args.no_latency and args.batch > 1:
+            X1, ids1, q1, roa1, R1 = make_batch(args.atoms, 1, 1000 * rank + 1, n0, args.order)
+            a = [torch.from_numpy(v).to(dev) for v in (X1, ids1, q1, roa1)]
+            def calls(n):
+                t1 = time.perf_counter()
+                for _ in range(n):
+                    model.forward_segments(a[0], a[1], a[2], a[3], R1)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t1) / n * 1e3
+            calls(3)
+            # a burst on an idle GPU: its first ten calls (what rounds 1 - 4 reported as ms_per_structure_batch1: 3 warm-up calls, 10 timed)
+            time.sleep(0.1)
+            lat_cold = calls(10)
+            # steady state of back-to-back calls: the clocks have ramped (about 30 calls, profiles/r05_clock_ramp.txt)
+            calls(30)
+            lat_ms = calls(50)
+            lat_detail = {"steady_state_ms": lat_ms, "calls": 50, "warmup_calls": 43,
+                          "first_10_calls_after_100ms_idle_ms": lat_cold,
+                          "note": "one model.forward_segments call per structure on device tensors, precision as the line; the GPU drops to its idle "
+                                  "clocks within tens of ms without work and needs ~30 calls to ramp back (profiles/r05_clock_ramp.txt)"}
 
     # ---- BASELINE config 4 as a strong-scaling leg (every world size runs the same list)
     stage[0] = "config-4 legs (sharding.forward_sharded)"
     cfg4 = cfg4_dense = cfg4_strong = None
-    if (not args.no_extras or args.mode == "strong") and args.config == "i_v4_1":
-        cfg4 = config4_leg(model, dist, args.backend, dev, args.config4_structures * world, max(3, min(args.steps, 5)), args.config4_max_atoms)
-        # the same list in the reference loader's OWN per-structure forms (dense one-hot q, bool M, int64 ids): every reduction inside the
-        # timed region (ADVICE r4 / VERDICT r4 item 6: the compact leg above pre-reduces outside it)
-        cfg4_dense = config4_leg(model, dist, args.backend, dev, args.config4_structures * world, 3, args.config4_max_atoms, forms="dense")
-        if world > 1:
-            # SURVEY 8e's acceptance is about a FIXED list (>= 7x on 8 GPUs, >= 64 structures): the same 512 structures at every world
-            # size, with the world-1 time of that list taken on rank 0 inside this run
-            cfg4_strong = config4_leg(model, dist, args.backend, dev, args.strong_structures, 3, args.config4_max_atoms, fixed_list=True)
+    if ((args.full and not args.no_extras) or args.mode == "strong") and args.config == "i_v4_1":
+        # (--mode strong: this leg is the headline - its gathered logits are what --dump-outputs writes besides z)
+        cfg4_out = {} if args.mode == "strong" and args.dump_outputs else None
+        cfg4 = config4_leg(model, dist, args.backend, dev, args.config4_structures * world, max(3, min(args.steps, 5)), args.config4_max_atoms,
+                           outputs=cfg4_out)
+        if cfg4_out:
+            dump_outputs(args.dump_outputs, cfg4_out)
+        if args.full:
+            # the same list in the reference loader's OWN per-structure forms (dense one-hot q, bool M, int64 ids): every reduction inside the
+            # timed region (ADVICE r4 / VERDICT r4 item 6: the compact leg above pre-reduces outside it)
+            cfg4_dense = config4_leg(model, dist, args.backend, dev, args.config4_structures * world, 3, args.config4_max_atoms, forms="dense")
+            if world > 1:
+                # SURVEY 8e's acceptance is about a FIXED list (>= 7x on 8 GPUs, >= 64 structures): the same 512 structures at every world
+                # size, with the world-1 time of that list taken on rank 0 inside this run
+                cfg4_strong = config4_leg(model, dist, args.backend, dev, args.strong_structures, 3, args.config4_max_atoms, fixed_list=True)
         if rank == 0 and cfg4 is not None:
             cfg4["dense_forms"] = cfg4_dense
 
@@ -883,6 +917,7 @@ def run(args, stage):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_structure": elapsed / n_struct * 1e3,
             "ms_per_structure_batch1": lat_ms,
@@ -926,7 +961,7 @@ def run(args, stage):
             # rank, and the weight broadcast every handle was built from
             "rccl_ranks_seen": ranks_info["ranks_seen"], "ranks": ranks_info, "weights_broadcast": wb,
         }
-        if args.cpu_budget > 0 and world == 1:      # the CPU baseline is a 1-GPU-run side measurement (rank 0, N = 1 only)
+        if args.full and args.cpu_budget > 0 and world == 1:      # the CPU baseline is a 1-GPU-run side measurement (rank 0, N = 1 only)
             key = {"i_v4_1": "2:", "i_v3_0": "3:"}.get(args.config, "2:")
             out["cpu_baseline"] = cpu_baseline(config, sd, args.atoms, args.cpu_budget, key)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]

@@ -1,9 +1,11 @@
-"""Print the A/B lines profiles/ab.sh left in gpurun_out/ab/: structures/s, ms per step, per-layer-class launch times."""
+"""Print the A/B lines profiles/ab.sh left in $PESTO_PROFILE_OUT/ab/ (default profiles/out/ab/): structures/s, ms per step,
+per-layer-class launch times."""
 import glob
 import json
+import os
 import sys
 
-for f in sorted(glob.glob((sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/ab") + "/*.json")):
+for f in sorted(glob.glob((sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.environ.get("PESTO_PROFILE_OUT", "profiles/out"), "ab")) + "/*.json")):
     try:
         d = json.load(open(f))
     except Exception as e:      # a build that crashed leaves an empty file

@@ -1,16 +1,17 @@
 #!/bin/bash
 # same box, N interleaved repetitions of 20 steps, medians per tag:  bash profiles/dev/ab_n.sh N tagA tagB ...  (libpesto_hip_<tag>.so)
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; rm -rf gpurun_out/ab; mkdir -p gpurun_out/ab
+export OUT=${PESTO_PROFILE_OUT:-profiles/out}; mkdir -p $OUT      # (results of this script: $OUT/...)
+R=$(cd "$(dirname "$0")/../.." && pwd); cd $R; rm -rf $OUT/ab; mkdir -p $OUT/ab
 N=$1; shift
 for rep in $(seq 1 $N); do for t in "$@"; do
-  PESTO_LIB=$R/pesto_amd/csrc/libpesto_hip_$t.so timeout 300 python bench.py --batch 8 --steps 20 --warmup 5 --cpu-budget 0 --no-extras --no-latency --no-check --precision f16_split > gpurun_out/ab/${t}_$rep.json 2>/dev/null
+  PESTO_LIB=$R/pesto_amd/csrc/libpesto_hip_$t.so timeout 300 python bench.py --full --batch 8 --steps 20 --warmup 5 --cpu-budget 0 --no-extras --no-latency --no-check --precision f16_split > $OUT/ab/${t}_$rep.json 2>/dev/null
 done; done
 python - "$@" <<'PY'
-import glob, json, sys
+import glob, json, os, sys
 import numpy as np
 for t in sys.argv[1:]:
     rows = []
-    for f in sorted(glob.glob(f"gpurun_out/ab/{t}_*.json")):
+    for f in sorted(glob.glob(os.environ["OUT"] + f"/ab/{t}_*.json")):
         try: d = json.load(open(f))
         except Exception: continue
         k = d["whole_forward"]["kernels"]

@@ -1,16 +1,17 @@
 #!/bin/bash
 # per-launch time of every layer kernel against the launch size (structures of 3,000 atoms per launch): the intercept is what a launch
 # costs before / after its steady state (launch, weight fill, first gathers, drain of the last centres).  bash profiles/dev/fixed_cost.sh
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out/fixed
+export OUT=${PESTO_PROFILE_OUT:-profiles/out}; mkdir -p $OUT      # (results of this script: $OUT/...)
+R=$(cd "$(dirname "$0")/../.." && pwd); cd $R; mkdir -p $OUT/fixed
 for b in 1 2 3 4 6 8 12 16 24; do
-  timeout 300 python bench.py --batch $b --steps 10 --warmup 3 --cpu-budget 0 --no-extras --no-latency > gpurun_out/fixed/b$b.json 2>/dev/null
+  timeout 300 python bench.py --full --batch $b --steps 10 --warmup 3 --cpu-budget 0 --no-extras --no-latency > $OUT/fixed/b$b.json 2>/dev/null
 done
 python - <<'PY'
-import json, numpy as np
+import json, os, numpy as np
 bs = [1, 2, 3, 4, 6, 8, 12, 16, 24]
 rows = {}
 for b in bs:
-    try: d = json.load(open(f"gpurun_out/fixed/b{b}.json"))
+    try: d = json.load(open(os.environ["OUT"] + f"/fixed/b{b}.json"))
     except Exception as e: print(b, "failed", e); continue
     wf = d.get("whole_forward", {})
     per = {int(k): v["avg_launch_ms"] * 1e3 for k, v in d["roofline"]["per_nn"].items()}

@@ -1,10 +1,10 @@
 #!/bin/bash
 # quick PMC: instruction counts per kernel for a tagged build
-R=$GRAFT_REPO_ROOT; export TMPDIR=/tmp; cd /tmp
+R=$(cd "$(dirname "$0")/../.." && pwd); export TMPDIR=/tmp; cd /tmp
 for t in "$@"; do
   LIBARG=""; [ "$t" != "default" ] && export PESTO_LIB=$R/pesto_amd/csrc/libpesto_hip_$t.so || unset PESTO_LIB
   rm -rf /tmp/pq_$t
-  timeout 240 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES -d /tmp/pq_$t -o pmc --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --cpu-budget 0 --no-latency --no-extras --no-check --precision f16_split > /tmp/pq_$t.log 2>&1
+  timeout 240 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES -d /tmp/pq_$t -o pmc --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --cpu-budget 0 --no-latency --no-extras --no-check --precision f16_split > /tmp/pq_$t.log 2>&1
   python - /tmp/pq_$t $t <<'PY'
 import csv, glob, re, sys, collections
 agg=collections.defaultdict(lambda: collections.defaultdict(float)); cnt=collections.Counter()

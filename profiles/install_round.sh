@@ -1,8 +1,8 @@
 #!/bin/bash
-# copy what profiles/prof_round.sh <tag> left under gpurun_out/<tag>/ into the tracked profiles/ directory
+# copy what profiles/prof_round.sh <tag> left under $PESTO_PROFILE_OUT/<tag>/ (default profiles/out/<tag>/) into the tracked profiles/ directory
 set -eu
 TAG=${1:-r05}
-S=gpurun_out/$TAG
+S=${PESTO_PROFILE_OUT:-profiles/out}/$TAG
 cp $S/kernel_stats.csv profiles/${TAG}_kernel_stats.csv
 cp $S/pmc_summary.txt profiles/${TAG}_pmc_summary.txt
 cp $S/pmc_readable.txt profiles/${TAG}_pmc_readable.txt

@@ -3,7 +3,7 @@
 (rocprofv3 --pmc, profiles/pmc_classes.sh) x the issue prices of profiles/microbench/r03_valu_cost.txt / r03_shadow.txt, at the clock
 the kernel actually ran at (GRBM_GUI_ACTIVE / 8 XCDs / duration of the same dispatch), against the measured launch time.
 
-    python profiles/issue_floor.py gpurun_out/<tag>/classes [bench.json [traffic.json]]  ->  markdown table on stdout; with a third
+    python profiles/issue_floor.py profiles/out/<tag>/classes [bench.json [traffic.json]]  ->  markdown table on stdout; with a third
     argument the per-kernel clock, predicted and measured launch times and their ratio are also written INTO that hash-stamped file
     (key "issue_floor"), which is where bench.py's roofline.issue_floor_ratio / roofline.clock_GHz come from
 

@@ -1,13 +1,14 @@
 #!/bin/bash
 # dynamic instruction CLASSES of the layer kernels (the input of profiles/issue_floor.py): three rocprofv3 --pmc passes of the bench workload
-# usage (GPU box, repo root): bash profiles/pmc_classes.sh <tag>   -> gpurun_out/<tag>/pmc_classes.json
+# usage (GPU box, repo root): bash profiles/pmc_classes.sh <tag>   -> $OUT/<tag>/pmc_classes.json
 set -u
 TAG=${1:-r05}
-R=${GRAFT_REPO_ROOT:-$(pwd)}
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${PESTO_PROFILE_OUT:-$R/profiles/out}      # results (prof_round.sh and the scripts it runs share it)
 export TMPDIR=/tmp
-mkdir -p $R/gpurun_out/$TAG/classes
+mkdir -p $OUT/$TAG/classes
 cd /tmp
-CMD="python $R/bench.py --steps 2 --warmup 1 --cpu-budget 0 --no-latency --no-extras --no-check --precision f16_split"
+CMD="python $R/bench.py --full --steps 2 --warmup 1 --cpu-budget 0 --no-latency --no-extras --no-check --precision f16_split"
 i=0
 for SET in \
   "SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64" \
@@ -16,9 +17,9 @@ for SET in \
   "GRBM_GUI_ACTIVE SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_STORE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU"
 do
   i=$((i+1))
-  timeout 240 rocprofv3 --pmc $SET -d $R/gpurun_out/$TAG/classes/p$i -o pmc --output-format csv -- $CMD > $R/gpurun_out/$TAG/classes/p$i.log 2>&1 || echo "pass $i failed"
+  timeout 240 rocprofv3 --pmc $SET -d $OUT/$TAG/classes/p$i -o pmc --output-format csv -- $CMD > $OUT/$TAG/classes/p$i.log 2>&1 || echo "pass $i failed"
 done
-python - "$R/gpurun_out/$TAG/classes" "$R/gpurun_out/$TAG/pmc_classes.json" <<'PY'
+python - "$OUT/$TAG/classes" "$OUT/$TAG/pmc_classes.json" <<'PY'
 import csv, glob, json, re, sys, collections
 root, out = sys.argv[1], sys.argv[2]
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.Counter()

@@ -1,16 +1,17 @@
 #!/bin/bash
 # PMC collection for the bench workload: separate rocprofv3 --pmc passes (no tracing combined), per
 # /opt/skills/guides/MI355X_MICROARCH.md (SQ 8 slots, TCC 4 slots; FETCH_SIZE costs 3, WRITE_SIZE 2).
-# usage: profiles/pmc_collect.sh <tag>   (run on the GPU box from the repo root; writes gpurun_out/pmc_<tag>/)
-# gpurun_out/pmc_<tag>/traffic.json is stamped with the sha256 of the kernel sources and the kernel symbols it saw; copy it to
+# usage: profiles/pmc_collect.sh <tag>   (run on the GPU box from the repo root; writes $OUT/pmc_<tag>/)
+# $OUT/pmc_<tag>/traffic.json is stamped with the sha256 of the kernel sources and the kernel symbols it saw; copy it to
 # profiles/traffic_i_v4_1_n3000_b8.json - bench.py quotes roofline.traffic from that file only while the hash matches the tree.
 set -u
 TAG=${1:-run}
-R=${GRAFT_REPO_ROOT:-$(pwd)}
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${PESTO_PROFILE_OUT:-$R/profiles/out}      # results (prof_round.sh and the scripts it runs share it)
 export TMPDIR=/tmp
 cd /tmp
-mkdir -p $R/gpurun_out/pmc_$TAG
-CMD="python $R/bench.py --steps 2 --warmup 1 --cpu-budget 0 --no-latency --no-extras --precision f16_split ${PESTO_BENCH_ARGS:-}"      # PESTO_BENCH_ARGS: e.g. "--edge-mode 3"
+mkdir -p $OUT/pmc_$TAG
+CMD="python $R/bench.py --full --steps 2 --warmup 1 --cpu-budget 0 --no-latency --no-extras --precision f16_split ${PESTO_BENCH_ARGS:-}"      # PESTO_BENCH_ARGS: e.g. "--edge-mode 3"
 i=0
 for SET in \
   "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES" \
@@ -20,9 +21,9 @@ for SET in \
   "WRITE_SIZE GRBM_GUI_ACTIVE"
 do
   i=$((i+1))
-  timeout 240 rocprofv3 --pmc $SET -d $R/gpurun_out/pmc_$TAG/p$i -o pmc --output-format csv -- $CMD > $R/gpurun_out/pmc_$TAG/p$i.log 2>&1 || echo "pass $i failed"
+  timeout 240 rocprofv3 --pmc $SET -d $OUT/pmc_$TAG/p$i -o pmc --output-format csv -- $CMD > $OUT/pmc_$TAG/p$i.log 2>&1 || echo "pass $i failed"
 done
-python - "$R/gpurun_out/pmc_$TAG" "$R" <<'PY'
+python - "$OUT/pmc_$TAG" "$R" <<'PY'
 import csv, glob, re, sys, collections
 root = sys.argv[1]
 sys.path.insert(0, sys.argv[2])

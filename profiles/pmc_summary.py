@@ -1,4 +1,4 @@
-"""Per-kernel summary of the rocprofv3 --pmc passes profiles/pmc_collect.sh left in a directory: python profiles/pmc_summary.py gpurun_out/pmc_<tag>"""
+"""Per-kernel summary of the rocprofv3 --pmc passes profiles/pmc_collect.sh left in a directory: python profiles/pmc_summary.py profiles/out/pmc_<tag>"""
 import collections
 import csv
 import glob

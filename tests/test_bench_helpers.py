@@ -63,3 +63,13 @@ def test_per_nn_table_and_rocprof_fraction():
     assert 'else "issue"' in src      # neither pipe half used: the line says instruction issue binds, not hbm
     assert '"frac_rocprof"' in src and '"per_nn"' in src and "speedup_vs_reference_equivalent_cpu_estimate" in src
     assert 'out["speedup_vs_reference_equivalent_cpu"]' not in src
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    """--dump-outputs: one <name>.npy per array, float32 (float64 kept), from numpy arrays and torch tensors alike."""
+    import numpy as np
+    import torch
+    bench.dump_outputs(str(tmp_path / "d"), {"z": torch.arange(6, dtype=torch.float16).reshape(3, 2), "w": np.ones(4), "v": np.arange(3)})
+    z, w, v = (np.load(str(tmp_path / "d" / f"{n}.npy")) for n in ("z", "w", "v"))
+    assert z.dtype == np.float32 and z.shape == (3, 2) and z[2, 1] == 5.0
+    assert w.dtype == np.float64 and v.dtype == np.float32 and sorted(os.listdir(str(tmp_path / "d"))) == ["v.npy", "w.npy", "z.npy"]

@@ -305,7 +305,7 @@ def test_sharded_hip_forward_equals_single_process_bitwise(tmp_path, backend, wo
         import subprocess
         env = dict(os.environ)
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--mode", "strong", "--steps", "3", "--warmup", "1", "--cpu-budget", "0",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--mode", "strong", "--full", "--steps", "3", "--warmup", "1", "--cpu-budget", "0",
                "--no-latency", "--config4-structures", "16", "--strong-structures", str(32 * world)]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert p.returncode == 0, p.stderr[-2000:]
@@ -363,7 +363,7 @@ def test_bench_launcher_two_ranks_on_one_gpu():
     import subprocess
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-gpu", "--backend", "gloo", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-gpu", "--backend", "gloo", "--full", "--steps", "2", "--warmup", "1",
            "--cpu-budget", "0", "--no-latency", "--config4-structures", "8", "--strong-structures", "24"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -390,6 +390,30 @@ def test_bench_launcher_two_ranks_on_one_gpu():
     assert dn["structures"] == 16 and dn["bitwise_equal_to_world1"] is True and dn["parity_max_abs_vs_reference"] < 1e-4 and "INSIDE the timed region" in dn["inputs"]
     cs = out["config4_strong"]
     assert cs["structures"] == 24 and cs["bitwise_equal_to_world1"] is True and cs["speedup_vs_world1"] > 0 and cs["scaling"].startswith("strong")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full) prints the headline line with its side legs null, and --dump-outputs
+    writes the logits of the LAST timed step: float32 [8 x 375, 5], structure 0 of which is the committed reference golden."""
+    import json
+    import subprocess
+    from conftest import golden
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["full"] is False and out["unit"] == "structures/s" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] * 1e-3 - 8) < 1e-6      # 8 structures per timed step
+    for key in ("roofline", "whole_forward", "long_sample", "segment_call", "batch1", "exact_fp32", "config4_sharded", "parity_max_abs"):
+        assert out[key] is None, key
+    assert "cpu_baseline" not in out
+    z = np.load(str(tmp_path / "out" / "z.npy"))
+    assert z.dtype == np.float32 and z.shape == (8 * 375, 5)
+    zg = golden("fwd_i_v4_1_stacked_synth3000")["z"]
+    assert np.abs(z[:zg.shape[0]] - zg).max() < 1e-4
 
 
 def test_bench_prints_one_json_error_line_instead_of_a_traceback():
