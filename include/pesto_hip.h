@@ -275,6 +275,39 @@ int pesto_postprocess(pesto_model* m, int64_t N, int64_t R, const float* z, cons
  * is asynchronous on `stream`; with host pointers it returns PESTO_ERR_INVALID itself. */
 int pesto_mask_to_segments(pesto_model* m, int64_t N, int64_t R, const float* M, int32_t* res_of_atom_out, int32_t ptr_kind, void* stream);
 
+/* ---- evaluation: interface labels and scores (no GPU counterpart in the reference) ----
+ * The two entry points below report their failures through pesto_eval_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). They use the handle for its device, after pesto_synchronize(m), and
+ * allocate their buffers stream-ordered per call, so they share no workspace with the forward. */
+const char* pesto_eval_last_error(void);
+
+/* replaces: the label side of the reference's dataset build and loader - extract_all_contacts / locate_contacts (src/data_encoding.py:116-176,
+ * one dense torch distance matrix per pair of subunits), contacts_types (processing/build_dataset.py:38-51) and load_interface_labels
+ * OR-ed over a subunit's partners (model/save/i_v4_1_2021-09-07_11-21/data_handler.py:9-23, 100-126) - for n_struct assemblies in one launch.
+ * Assembly s owns atoms [struct_offsets[s], struct_offsets[s+1]) (HOST array, n_struct + 1 entries). Per atom: X float32 [n_total,3],
+ * subunit int32 (any id; atoms of one subunit share it), residue int32 (the batch-global label row of a receptor atom, in [0, n_res)),
+ * receptor uint8 (!= 0: the atom's resname is one of l_types) and partner_mask uint32 (bit c: the resname is one of r_types[c]; 0 = never a
+ * partner). Result: labels_out uint32 [n_res] (cleared by the call),
+ *     labels_out[residue[a]] |= partner_mask[b]   for every receptor atom a and atom b of the same assembly, subunit[b] != subunit[a],
+ *                                                 with the fp32 distance sqrt(fma(z,z, fma(y,y, x*x))) (torch.norm's rounding) < r_thr
+ * and ties_out uint8 [n_total]: 1 where a receptor atom has such a partner at EXACTLY r_thr - the pairs on which a distance rounded another
+ * way could decide the label. Cell grid (cells >= r_thr wide), one thread per atom in cell order; OR is order-free, so the result is
+ * deterministic. Both paths synchronise `stream` (the offsets and the error word are host memory of the call); a receptor atom with a
+ * residue outside [0, n_res) makes the call return PESTO_ERR_INVALID (with device pointers its contacts are skipped, nothing else). */
+int pesto_interface_labels(pesto_model* m, int64_t n_total, int32_t n_struct, const int32_t* struct_offsets, const float* X,
+                           const int32_t* subunit, const int32_t* residue, const uint8_t* receptor, const uint32_t* partner_mask,
+                           int64_t n_res, float r_thr, uint32_t* labels_out, uint8_t* ties_out, int32_t ptr_kind, void* stream);
+
+/* replaces: bc_scoring (src/scoring.py:77-96: torch counts and sklearn's roc_auc_score on the host, one structure at a time) for n_struct
+ * structures in one launch. Structure s owns rows [res_offsets[s], res_offsets[s+1]) (HOST array, every structure >= 1 row) of
+ * y uint8 [R,n_class] (0 / non-zero) and p float32 [R,n_class] (probabilities, finite). scores_out float32 [n_struct,8,n_class], rows
+ * acc, ppv, npv, tpr, tnr, mcc, auc, std (bc_score_names): q = round(p) half to even; exact integer TP / TN / FP / FN; ppv NaN without
+ * positives, npv NaN without negatives, +-inf -> NaN for tpr / tnr / mcc, 0/0 NaN; mcc in the reference's float32 operation order;
+ * auc = Mann-Whitney U / (P N) with ties 1/2, 2U counted exactly over every (positive, negative) pair (NaN unless P > 0 and N > 0);
+ * std = torch.std (unbiased, fp64 accumulation; NaN for one row). One workgroup per (structure, class). The call synchronises `stream`. */
+int pesto_bc_scores(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const uint8_t* y, const float* p,
+                    float* scores_out, int32_t ptr_kind, void* stream);
+
 /* ---- test hooks ----
  * Debug twins of the shipped kernels, selected per handle (the parity tests run every stage through each of them):
  * layer_kernels 0 = shipped (hybrid first layer; arithmetic per the precision policy), 1 = reference-formulation fp32 VALU

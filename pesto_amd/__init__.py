@@ -5,11 +5,15 @@ here: a Python host mirror of the reference Module API over a C-ABI HIP library.
 """
 from .config import CONFIGS, config_i_v3_0, config_i_v3_1, config_i_v4_0, config_i_v4_1, config_model  # noqa: F401
 
-__all__ = ["Model", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
+__all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_assemblies", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch or the built library
     if name == "Model":
         from .model import Model
         return Model
+    if name in ("evaluate", "interface_labels", "bc_scoring", "benchmark_assemblies"):
+        import importlib
+        ev = importlib.import_module(".evaluate", __name__)
+        return ev if name == "evaluate" else getattr(ev, name)
     raise AttributeError(name)
