@@ -308,6 +308,40 @@ int pesto_interface_labels(pesto_model* m, int64_t n_total, int32_t n_struct, co
 int pesto_bc_scores(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const uint8_t* y, const float* p,
                     float* scores_out, int32_t ptr_kind, void* stream);
 
+/* ---- interface patches (no GPU counterpart in the reference) ----
+ * Failures of the entry point below are reported through pesto_patches_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the evaluation group it uses the handle for its device, after
+ * pesto_synchronize(m), and allocates its buffers stream-ordered per call. */
+const char* pesto_patches_last_error(void);
+
+enum {
+    PESTO_PATCHES_SMALL_MAX = 4096,       /* structures of at most this many rows: one workgroup per (structure, selection), all in LDS */
+    PESTO_PATCHES_MAX_CLASSES = 1024,
+    PESTO_PATCHES_MAX_SEL = 1024,
+    PESTO_PATCHES_MAX_ROWS = 0x3ffffff0,
+    PESTO_PATCHES_FORCE_LARGE = 1         /* flags bit: every structure takes the large-structure path (test hook) */
+};
+
+/* replaces: cluster_interfaces and cluster_multi_interfaces with follow_rabbit / follow_rabbits (interfaceome/cluster_interfaces.py:9-56,
+ * interfaceome/cluster_multi_interfaces.py:9-61: a dense NumPy distance matrix and a set-based search per structure and selection) for
+ * n_struct structures and n_sel selections in one call. Structure s owns rows [res_offsets[s], res_offsets[s+1]) (HOST array, n_struct + 1
+ * entries, every structure >= 1 row; R = res_offsets[n_struct] <= PESTO_PATCHES_MAX_ROWS, R * n_class and R * n_sel < 2^31) of
+ * xyz float32 [R,3] (the residue's CA), p float32 [R,n_class], afs float32 [R] (confidence, e.g. pLDDT; NULL: no confidence test) and
+ * has_ca uint8 [R] (0: the residue has no CA and is never a node; NULL: every residue has one). sel int32 [n_sel,2] (HOST) lists the
+ * class pairs (i, j), 0 <= i <= j < n_class <= PESTO_PATCHES_MAX_CLASSES, n_sel <= PESTO_PATCHES_MAX_SEL. For selection k = (i, j):
+ *     node r      afs[r] > afs_thr && has_ca[r] && p[r,i] > p_thr && p[r,j] > p_thr      (float32, strict; NaN never passes)
+ *     edge (a,b)  sqrt((dx*dx + dy*dy) + dz*dz) < d_thr, every operation rounded to float32 (NumPy's distance matrix); d_thr > 0 finite
+ *     patches     the connected components, numbered 0, 1, ... in the order of their smallest member row (follow_rabbits' order)
+ * Outputs: patch_of int32 [n_sel,R] (patch number of the row within its (structure, selection), -1 for rows that are not nodes),
+ * n_patches int32 [n_struct,n_sel], patch_size int32 [n_sel,R] and patch_mean float32 [n_sel,R,2] (size and the mean of p[:,i], p[:,j] over
+ * the members, summed in double, at each patch's smallest member row; 0 at every other row). Every output is bit-identical from call to
+ * call. Structures of more than PESTO_PATCHES_SMALL_MAX rows spread their node-pair tiles over many workgroups. flags: 0 or
+ * PESTO_PATCHES_FORCE_LARGE. The call synchronises `stream`. */
+int pesto_interface_patches(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const float* xyz, const float* p,
+                            const float* afs, const uint8_t* has_ca, int32_t n_sel, const int32_t* sel, float afs_thr, float p_thr, float d_thr,
+                            int32_t* patch_of, int32_t* n_patches, int32_t* patch_size, float* patch_mean, int32_t flags, int32_t ptr_kind,
+                            void* stream);
+
 /* ---- test hooks ----
  * Debug twins of the shipped kernels, selected per handle (the parity tests run every stage through each of them):
  * layer_kernels 0 = shipped (hybrid first layer; arithmetic per the precision policy), 1 = reference-formulation fp32 VALU

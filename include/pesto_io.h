@@ -62,6 +62,9 @@ int pesto_io_preprocess(pesto_structure* s, int32_t steps);
 int pesto_io_n_atoms(const pesto_structure* s, int64_t* n);
 int pesto_io_get_xyz(const pesto_structure* s, float* xyz /*[N,3]*/);
 int pesto_io_get_resid(const pesto_structure* s, int64_t* resid /*[N]*/);
+/* the b-factor column (61-66) of each atom's record, carried through preprocessing (0 where the line is shorter, and for a structure built
+ * from arrays). Neither the reference's read_pdb nor its structure dict keeps it; its interfaceome scripts read AlphaFold's pLDDT from it. */
+int pesto_io_get_bfactor(const pesto_structure* s, float* bfactor /*[N]*/);
 /* copies a text field as fixed-width NUL-padded records of `width` bytes (longer values are an error) */
 int pesto_io_get_text(const pesto_structure* s, int32_t field, char* out, int32_t width);
 

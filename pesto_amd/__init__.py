@@ -5,7 +5,8 @@ here: a Python host mirror of the reference Module API over a C-ABI HIP library.
 """
 from .config import CONFIGS, config_i_v3_0, config_i_v3_1, config_i_v4_0, config_i_v4_1, config_model  # noqa: F401
 
-__all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_assemblies", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
+__all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_assemblies", "patches", "interface_patches",
+           "interface_patches_batch", "residue_ca", "save_patches", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch or the built library
@@ -16,4 +17,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         ev = importlib.import_module(".evaluate", __name__)
         return ev if name == "evaluate" else getattr(ev, name)
+    if name in ("patches", "interface_patches", "interface_patches_batch", "residue_ca", "save_patches"):
+        import importlib
+        pa = importlib.import_module(".patches", __name__)
+        return pa if name == "patches" else getattr(pa, name)
     raise AttributeError(name)

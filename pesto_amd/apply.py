@@ -20,6 +20,15 @@ def _load(path, n0):
     return s, X, q, roa, R
 
 
+def _load_ca(path, n0):
+    """_load plus, per residue row, the CA atom (-1: none) and the CA's b-factor (AlphaFold: pLDDT) for interface patches"""
+    from .patches import residue_ca
+    s, X, q, roa, R = _load(path, n0)
+    _, has, ca = residue_ca(s)
+    afs = np.where(has != 0, s.bfactor()[np.maximum(ca, 0)], np.float32(0)).astype(np.float32)
+    return s, X, q, roa, R, ca, afs
+
+
 def _is_h5(path):
     return os.fspath(path).lower().endswith((".h5", ".hdf5", ".hdf"))
 
@@ -101,7 +110,7 @@ def load_results(path):
 
 
 def apply_model(model, pdb_filepaths, write=True, suffix="_i{}.pdb", max_atoms=24576, workers=8, on_error=print, results_path=None,
-                report_ties=True):
+                report_ties=True, patches_path=None, patch_args=None):
     """Returns {path: p} with p = sigmoid(z) as numpy [R, n_out] for every structure that could be processed.
     write=True also saves ``path[:-4] + suffix.format(i)`` for each output channel i (apply_model.ipynb:157-166).
     results_path: also write all probability tables into one bulk result file (save_results): ``*.h5`` = the reference's HDF5 store
@@ -109,10 +118,21 @@ def apply_model(model, pdb_filepaths, write=True, suffix="_i{}.pdb", max_atoms=2
     ``model``: a pesto_amd.Model on a GPU; max_atoms: atoms per launch (about 24k fills an MI355X).
     report_ties: log (logging "pesto_amd.apply", WARNING) the structures in which two neighbours at exactly the same float32 distance
     straddle a layer's neighbourhood cut-off - the rows on which the reference's torch.topk (src/data_encoding.py:98-99) may have chosen
-    the other atom, the one known source of logit differences beyond 1e-4 against the reference (pesto_knn_tie_rows)."""
+    the other atom, the one known source of logit differences beyond 1e-4 against the reference (pesto_knn_tie_rows).
+    patches_path: also compute the interface patches of every structure on the device, from the p each launch holds and the CA rows of
+    the coordinates already on the GPU (pesto_amd.patches), and write them with save_patches, keyed by path: the reference's
+    clustered_multi_interfaces.json layout (clustered_interfaces.json with patch_args={"pairs": False}). patch_args: pairs (True),
+    afs_thr, p_thr, d_thr (70, 0.5, 10) and use_afs (False; True: the CA b-factor is the confidence, as for AlphaFold models).
+    Without patches_path nothing of this runs and the return value is the same."""
     import torch
     pdb_filepaths = list(pdb_filepaths)
     check_results_path(results_path, pdb_filepaths)      # no HDF5 library / colliding dataset names: raised now, not after the run
+    patch_args = dict(patch_args or {})
+    if patches_path is not None:
+        unknown = set(patch_args) - {"pairs", "afs_thr", "p_thr", "d_thr", "use_afs"}
+        if unknown:
+            raise ValueError(f"unknown patch_args {sorted(unknown)}")
+    patches = {} if patches_path is not None else None
     n0 = model.config["em"]["N0"]
     dev = torch.device("cuda", model._gpu)
     results = {}
@@ -121,7 +141,7 @@ def apply_model(model, pdb_filepaths, write=True, suffix="_i{}.pdb", max_atoms=2
     was_async = model.async_auto
     model.set_async_auto(True)
     try:
-        _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_error, results, dev, n0, report_ties)
+        _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_error, results, dev, n0, report_ties, patches, patch_args)
     except BaseException:
         # the loop failed: still drain the handle and restore its mode, but the deferred check of the last launch (model.synchronize() may
         # raise its bad-input / range error) must not replace the exception that is already in flight
@@ -143,17 +163,20 @@ def apply_model(model, pdb_filepaths, write=True, suffix="_i{}.pdb", max_atoms=2
         except Exception as e:      # (checked up front; what is left is the file system) - the computed tables are not lost with it
             e.results = results
             raise
+    if patches is not None:
+        from .patches import save_patches
+        save_patches(patches_path, {k: patches[k] for k in results})
     return results
 
 
-def _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_error, results, dev, n0, report_ties):
+def _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_error, results, dev, n0, report_ties, patches=None, patch_args=None):
     import logging
     log = logging.getLogger("pesto_amd.apply")
     used_cuts = sorted({int(l["nn"]) for l in model.config["sum"]})
     cut_mask = sum(1 << {8: 0, 16: 1, 32: 2, 64: 3}[c] for c in used_cuts)
     import torch
     with ThreadPoolExecutor(max_workers=workers) as pool:
-        loads = [(p, pool.submit(_load, p, n0)) for p in pdb_filepaths]
+        loads = [(p, pool.submit(_load if patches is None else _load_ca, p, n0)) for p in pdb_filepaths]
         writes = []
 
         # One launch = pack (host) -> H2D, GPU k-NN, forward (queued, asynchronous) -> fetch (post-op, D2H) -> hand out (slice, b-factor
@@ -167,9 +190,25 @@ def _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_erro
             """post-op + D2H of the launch in flight -> host arrays (None when nothing is in flight)"""
             if not in_flight:
                 return None
-            group, sizes, r_off, z, roa, ties = in_flight.pop()
+            group, sizes, r_off, z, roa, ties, ca_xyz = in_flight.pop()
             p, bf = model.postprocess(z, roa)
-            return group, sizes, r_off, p.cpu().numpy(), bf.cpu().numpy(), (ties.cpu().numpy() if ties is not None else None)
+            out = group, sizes, r_off, p.cpu().numpy(), bf.cpu().numpy(), (ties.cpu().numpy() if ties is not None else None)
+            if patches is not None:
+                patch_group(group, r_off, p, ca_xyz)
+            return out
+
+        def patch_group(group, r_off, p, ca_xyz):
+            """interface patches of a launch on the device: p rows and the CA coordinates gathered from the launch's X"""
+            from .patches import interface_patches_batch
+            pa = dict(patch_args)
+            use_afs = pa.pop("use_afs", False)
+            n = len(group)
+            ps = [p[r_off[i]:r_off[i + 1]] for i in range(n)]
+            xs = [ca_xyz[r_off[i]:r_off[i + 1]] for i in range(n)]
+            has = [torch.from_numpy((g[6] >= 0).astype(np.uint8)).to(dev) for g in group]
+            afss = [torch.from_numpy(g[7]).to(dev) for g in group] if use_afs else None
+            for (path, *_rest), pl in zip(group, interface_patches_batch(model, ps, xs, afss, has, **pa)):
+                patches[path] = pl
 
         def hand_out(done):
             """slice a fetched launch per structure, queue its b-factor files (host only: runs while the GPU computes the next launch)"""
@@ -202,7 +241,12 @@ def _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_erro
             ids = model.knn_collate(X, sizes)
             ties = model.knn_tie_rows(X, sizes, ids) if report_ties else None
             z = model.forward_segments(X, ids, q, roa, int(r_off[-1]), sizes=sizes)    # one call per structure, semantically
-            in_flight.append((group, sizes, r_off, z, roa, ties))
+            ca_xyz = None
+            if patches is not None:                  # CA rows of the coordinates already on the device (row 0 where a residue has none)
+                a_off = np.cumsum([0] + sizes)
+                ca = np.concatenate([np.where(g[6] >= 0, g[6] + a_off[i], 0) for i, g in enumerate(group)])
+                ca_xyz = X[torch.from_numpy(ca).to(dev)]
+            in_flight.append((group, sizes, r_off, z, roa, ties, ca_xyz))
             hand_out(done)
 
         group, atoms = [], 0
@@ -211,7 +255,7 @@ def _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_erro
                                         # repeats them on the exact kernels, and that repeat covers the whole launch (sharding.forward_local)
         for path, fut in loads:
             try:
-                s, X, q, roa, R = fut.result()
+                s, X, q, roa, R, *ca = fut.result()
             except (PestoIOError, OSError) as e:
                 if on_error:
                     on_error(f"error with {path}: {e}")
@@ -220,13 +264,13 @@ def _apply_loop(model, pdb_filepaths, write, suffix, max_atoms, workers, on_erro
                 if small and small_atoms + len(s) > max_atoms:
                     flush(small)
                     small, small_atoms = [], 0
-                small.append((path, s, X, q, roa, R))
+                small.append((path, s, X, q, roa, R, *ca))
                 small_atoms += len(s)
                 continue
             if group and atoms + len(s) > max_atoms:
                 flush(group)
                 group, atoms = [], 0
-            group.append((path, s, X, q, roa, R))
+            group.append((path, s, X, q, roa, R, *ca))
             atoms += len(s)
         flush(group)
         flush(small)

@@ -94,13 +94,14 @@ struct Atoms {
     std::vector<std::string> name, element, resname, chain, icode;
     std::vector<int64_t> resid;
     std::vector<char> het;    // 'A' (ATOM) or 'H' (HETATM)
+    std::vector<float> bfactor;   // columns 61-66 of the record (0 where absent or built from arrays); not part of the reference's dict
     bool has_icode = true;    // clean_structure pops "icode"
     size_t size() const { return resid.size(); }
 
     void push_from(const Atoms& o, size_t i) {
         xyz.insert(xyz.end(), o.xyz.begin() + 3 * i, o.xyz.begin() + 3 * i + 3);
         name.push_back(o.name[i]); element.push_back(o.element[i]); resname.push_back(o.resname[i]);
-        chain.push_back(o.chain[i]); resid.push_back(o.resid[i]); het.push_back(o.het[i]);
+        chain.push_back(o.chain[i]); resid.push_back(o.resid[i]); het.push_back(o.het[i]); bfactor.push_back(o.bfactor[i]);
         if (o.has_icode) icode.push_back(o.icode[i]);
     }
     Atoms select(const std::vector<size_t>& idx) const {
@@ -196,7 +197,7 @@ bool record_is(const char* line, int len, const char* rec4) {   // first four co
     return true;
 }
 
-struct PAtom { std::string name; const char* element; char altloc; float x, y, z; };
+struct PAtom { std::string name; const char* element; char altloc; float x, y, z, b; };
 struct PRes { int num; char icode; std::string name, segment; char het; std::vector<PAtom> atoms; };
 struct PChain { std::string name; std::vector<PRes> res; };
 struct PModel { std::string name; std::vector<PChain> chains; };
@@ -253,6 +254,7 @@ int parse_pdb(const char* text, int64_t n, std::vector<PModel>& models) {
             a.x = (float)read_double(line, len, 30, 8);
             a.y = (float)read_double(line, len, 38, 8);
             a.z = (float)read_double(line, len, 46, 8);
+            a.b = len > 60 ? (float)read_double(line, len, 60, 6) : 0.f;
             char pad[4] = {' ', ' ', ' ', ' '};
             for (int i = 0; i < 4 && 12 + i < len; ++i) pad[i] = line[12 + i];
             if (len > 76 && (std::isalpha((unsigned char)line[76]) || (len > 77 && std::isalpha((unsigned char)line[77])))) {
@@ -308,6 +310,7 @@ int models_to_atoms(const std::vector<PModel>& models, Atoms& out) {
                     out.resname.push_back(r.name);
                     out.resid.push_back(r.num);
                     out.het.push_back(r.het);
+                    out.bfactor.push_back(a.b);
                     out.chain.push_back(c.name + ":" + std::to_string(mid));
                 }
     return 0;
@@ -583,6 +586,7 @@ int pesto_io_from_arrays(int64_t n, const float* xyz, const int64_t* resid, cons
         a.element.push_back(get(PESTO_IO_ELEMENT, i));
         a.resname.push_back(get(PESTO_IO_RESNAME, i));
         a.het.push_back(get(PESTO_IO_HET_FLAG, i) == "H" ? 'H' : 'A');
+        a.bfactor.push_back(0.f);
         a.chain.push_back(get(PESTO_IO_CHAIN_NAME, i));
         if (a.has_icode) a.icode.push_back(get(PESTO_IO_ICODE, i));
     }
@@ -616,6 +620,12 @@ int pesto_io_get_xyz(const pesto_structure* s, float* xyz) {
 int pesto_io_get_resid(const pesto_structure* s, int64_t* resid) {
     if (!s || !resid) return fail(PESTO_IO_ERR_INVALID, "bad arguments");
     std::copy(s->a.resid.begin(), s->a.resid.end(), resid);
+    return 0;
+}
+
+int pesto_io_get_bfactor(const pesto_structure* s, float* bfactor) {
+    if (!s || !bfactor) return fail(PESTO_IO_ERR_INVALID, "bad arguments");
+    std::copy(s->a.bfactor.begin(), s->a.bfactor.end(), bfactor);
     return 0;
 }
 

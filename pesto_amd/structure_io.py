@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "pesto_io_last_error", "pesto_io_read_pdb", "pesto_io_parse_pdb", "pesto_io_from_arrays", "pesto_io_free",
     "pesto_io_preprocess", "pesto_io_n_atoms", "pesto_io_get_xyz", "pesto_io_get_resid", "pesto_io_get_text",
     "pesto_io_encode", "pesto_io_write_pdb", "pesto_io_format_pdb", "pesto_io_mask_to_segments", "pesto_io_mask_to_segments_any",
+    "pesto_io_get_bfactor",
 ]
 
 _lib = None
@@ -55,6 +56,7 @@ def load():
     lib.pesto_io_n_atoms.argtypes = [c_p, P(i64)]
     lib.pesto_io_get_xyz.argtypes = [c_p, c_p]
     lib.pesto_io_get_resid.argtypes = [c_p, c_p]
+    lib.pesto_io_get_bfactor.argtypes = [c_p, c_p]
     lib.pesto_io_get_text.argtypes = [c_p, i32, c_p, i32]
     lib.pesto_io_encode.argtypes = [c_p, i32, c_p, c_p, c_p, P(i64)]
     lib.pesto_io_write_pdb.argtypes = [c_p, c_p, i64, ctypes.c_char_p]
@@ -155,6 +157,13 @@ class Structure:
         except PestoIOError:
             pass
         return d
+
+    def bfactor(self):
+        """float32 [N]: each atom's b-factor column (61-66) from the file, through preprocessing (0 for a structure built from a dict). For
+        AlphaFold models it holds the pLDDT. Not part of to_dict(), whose keys mirror the reference's structure dict."""
+        bf = np.empty(len(self), np.float32)
+        _check(load().pesto_io_get_bfactor(self._h, bf.ctypes.data))
+        return bf
 
     def subunits(self):
         """split_by_chain (src/structure.py:63-80): {chain_name: structure dict without 'chain_name'} in sorted-name order."""
