@@ -1,10 +1,12 @@
-"""ctypes binding of libpesto_hip.so (the C ABI declared in include/pesto_hip.h).
+"""ctypes binding of libpesto_hip.so (the C ABI declared in include/pesto_hip.h), and where a call's arrays live (Side).
 
 The library is built in-tree by ``python -m pesto_amd.csrc.build`` (hipcc --offload-arch=gfx950) and
 must be present: there is NO fallback path - a missing library raises at first use.
 """
 import ctypes
 import os
+
+import numpy as np
 
 from .config import MAX_LAYERS, normalise
 
@@ -142,9 +144,129 @@ def load():
     return lib
 
 
-def check(rc):
+def check(rc, last_error=None):
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message (default pesto_last_error; the
+    evaluation and patch entry points keep their own, pesto_eval_last_error / pesto_patches_last_error)."""
     if rc != 0:
-        msg = load().pesto_last_error()
+        msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")
         err.code = rc
         raise err
+
+
+# ------------------------------------------------------------------ host / device marshalling
+def is_torch(x):
+    return hasattr(x, "detach") and hasattr(x, "device")
+
+
+def host(a):
+    """``a`` as a numpy array (a torch tensor is detached and copied to the host first)."""
+    return a.detach().cpu().numpy() if is_torch(a) else np.asarray(a)
+
+
+def offsets(sizes):
+    """int32 [len(sizes) + 1]: the exclusive prefix sum of ``sizes`` (the structure offsets the entry points take, always host memory)."""
+    sizes = [int(v) for v in sizes]
+    offs = np.zeros(len(sizes) + 1, np.int32)
+    offs[1:] = np.cumsum(sizes)
+    return offs
+
+
+def ids_kind(ids):
+    """IDS_INT64 / IDS_INT32 of a neighbour table that put() placed as (np.int64, np.int32)."""
+    return IDS_INT64 if str(ids.dtype).endswith("int64") else IDS_INT32
+
+
+def _torch_dtype(dtype):
+    import torch
+    return torch.int32 if dtype == np.uint32 else getattr(torch, dtype.name)      # (uint32 travels as the int32 of the same bits)
+
+
+class Side:
+    """The memory of ONE library call, decided by its lead array (X, X_frames, z, M or ps[0]). A ROCm lead puts the call on the device:
+    device pointers, torch's current stream of the lead's GPU, which must be the handle's ``gpu`` (RuntimeError otherwise). Any other lead
+    puts it on the host: host pointers, stream None; the library stages the arrays. Every array of the call goes through put() / cat() /
+    empty(), so it lives on the call's side: with a ROCm lead a host array is copied to the device, never passed as a host pointer."""
+
+    def __init__(self, lead, gpu):
+        self.torch_lead = is_torch(lead)
+        self.device, self.stream, self.kind = None, None, PTR_HOST
+        if self.torch_lead and lead.is_cuda:
+            import torch
+            if lead.device.index != gpu:
+                raise RuntimeError(f"inputs are on cuda:{lead.device.index} but the model is on cuda:{gpu} (use .to())")
+            self.device, self.kind = lead.device, PTR_DEVICE
+            self.stream = torch.cuda.current_stream(self.device).cuda_stream
+
+    def _tensor(self, a, dtype):
+        """a as a torch tensor of dtype on this side's GPU (not necessarily contiguous)"""
+        import torch
+        if not is_torch(a):
+            a = np.asarray(a, dtype)
+            a = torch.from_numpy(np.ascontiguousarray(a.view(np.int32) if dtype == np.uint32 else a))
+        return a.detach().to(device=self.device, dtype=_torch_dtype(dtype))
+
+    def put(self, a, dtype, shape=None, name="array", strided=False):
+        """``a`` (numpy, CPU / ROCm tensor, list) as a contiguous array of ``dtype`` on this side: a numpy array on the host, a tensor on
+        the device (uint32 as the int32 of the same bits). ``a`` itself comes back when it is one already - no copy, no kernel.
+        dtype: one numpy dtype, or a tuple of those the call takes (``a``'s own if it is one of them, else the first).
+        shape: the shape the call needs (ValueError otherwise). strided: a view whose innermost axis is contiguous is kept as it is
+        (read in place; element strides: strides())."""
+        if isinstance(dtype, tuple):
+            own = str(a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype).replace("torch.", "")
+            dtype = next((d for d in dtype if np.dtype(d).name == own), dtype[0])
+        dtype = np.dtype(dtype)
+        if self.device is None:
+            out = host(a)
+            if not (strided and out.dtype == dtype and out.ndim and out.strides[-1] == out.itemsize
+                    and all(s % out.itemsize == 0 for s in out.strides)):
+                out = np.ascontiguousarray(out, dtype=dtype)
+        else:
+            out = a
+            if not (is_torch(a) and a.device == self.device and a.dtype == _torch_dtype(dtype)
+                    and (a.stride(-1) == 1 if strided else a.is_contiguous())):
+                out = self._tensor(a, dtype).contiguous()
+        if shape is not None and tuple(out.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {list(shape)}, got {list(out.shape)}")
+        return out
+
+    def cat(self, arrays, dtype):
+        """The arrays one after the other along axis 0, as put(): one contiguous array of ``dtype`` on this side."""
+        dtype = np.dtype(dtype)
+        if self.device is None:
+            return np.ascontiguousarray(np.concatenate([host(a) for a in arrays]), dtype=dtype)
+        import torch
+        return torch.cat([self._tensor(a, dtype) for a in arrays]).contiguous()
+
+    def empty(self, shape, dtype):
+        """An uninitialised output array on this side."""
+        if self.device is None:
+            return np.empty(shape, dtype)
+        import torch
+        return torch.empty(shape, dtype=_torch_dtype(np.dtype(dtype)), device=self.device)
+
+    def ptr(self, a):
+        """The address the library reads / writes ``a`` at (None: NULL). Refuses, before any library call, an array of the other side:
+        a device call takes tensors on its GPU only, a host call numpy arrays only."""
+        if a is None:
+            return None
+        if self.device is None:
+            if not isinstance(a, np.ndarray):
+                raise RuntimeError(f"a host call takes numpy arrays, got {type(a).__name__}")
+            return a.ctypes.data
+        if not (is_torch(a) and a.device == self.device):
+            where = a.device if is_torch(a) else type(a).__name__
+            raise RuntimeError(f"a device call on {self.device} takes tensors on that GPU, got {where}")
+        return a.data_ptr()
+
+    def result(self, a):
+        """An output as the lead's kind: a CPU tensor for a CPU-tensor lead, else ``a`` as it is."""
+        if a is None or self.device is not None or not self.torch_lead:
+            return a
+        import torch
+        return torch.from_numpy(a)
+
+
+def strides(a):
+    """Element strides of a numpy array or a torch tensor."""
+    return tuple(a.stride()) if is_torch(a) else tuple(s // a.itemsize for s in a.strides)

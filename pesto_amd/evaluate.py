@@ -35,23 +35,6 @@ BC_SCORE_NAMES = ["acc", "ppv", "npv", "tpr", "tnr", "mcc", "auc", "std"]      #
 MAX_CLASSES = 32
 
 
-def _is_torch(x):
-    return hasattr(x, "detach") and hasattr(x, "device")
-
-
-def _check(rc):
-    """_lib.check for the evaluation entry points (their message: pesto_eval_last_error)"""
-    if rc != 0:
-        msg = _lib.load().pesto_eval_last_error()
-        err = _lib.PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")
-        err.code = rc
-        raise err
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
-
-
 _scoring_models = {}
 
 
@@ -82,38 +65,23 @@ def resname_masks(resnames, l_types=L_TYPES, r_types=R_TYPES):
 
 def contact_labels(model, X, subunit, residue, receptor, partner_mask, sizes, n_res, r_thr=R_THR):
     """pesto_interface_labels on a batch of assemblies (``sizes`` atoms each, concatenated): (labels uint32 [n_res], ties uint8 [N]).
-    ROCm tensors run on the GPU buffers as they are (device pointers, torch's current stream); numpy / CPU tensors are staged."""
+    X decides where the call runs (pesto_amd._lib.Side): a ROCm X runs on the GPU buffers as they are (device pointers, torch's current
+    stream; the other arrays are copied to its GPU where needed; labels: the int32 of the uint32 bits); numpy / CPU tensors are staged."""
     h = model.handle
-    lib = _lib.load()
-    offs = np.zeros(len(sizes) + 1, np.int32)
-    offs[1:] = np.cumsum([int(v) for v in sizes])
+    offs = _lib.offsets(sizes)
     n = int(offs[-1])
-    if _is_torch(X) and X.is_cuda:
-        import torch
-        dev = X.device
-        t = lambda a, dt: (a if _is_torch(a) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=dt).contiguous()
-        Xc = t(X, torch.float32)
-        su, rs, rc = t(subunit, torch.int32), t(residue, torch.int32), t(receptor, torch.uint8)
-        pm = t(torch.as_tensor(np.asarray(partner_mask, np.uint32).view(np.int32)) if not _is_torch(partner_mask) else partner_mask, torch.int32)
-        if tuple(Xc.shape) != (n, 3) or any(int(a.numel()) != n for a in (su, rs, rc, pm)):
-            raise ValueError(f"X must be [{n},3] and the per-atom arrays [{n}]")
-        labels = torch.empty((int(n_res),), dtype=torch.int32, device=dev)
-        ties = torch.empty((n,), dtype=torch.uint8, device=dev)
-        _check(lib.pesto_interface_labels(h, n, len(sizes), offs.ctypes.data, Xc.data_ptr(), su.data_ptr(), rs.data_ptr(), rc.data_ptr(),
-               pm.data_ptr(), int(n_res), float(r_thr), labels.data_ptr(), ties.data_ptr(), _lib.PTR_DEVICE,
-               torch.cuda.current_stream(dev).cuda_stream))
-        return labels, ties
-    Xn = np.ascontiguousarray(_host(X), dtype=np.float32)
-    su = np.ascontiguousarray(_host(subunit), dtype=np.int32)
-    rs = np.ascontiguousarray(_host(residue), dtype=np.int32)
-    rc = np.ascontiguousarray(_host(receptor), dtype=np.uint8)
-    pm = np.ascontiguousarray(_host(partner_mask).astype(np.uint32))
-    if Xn.shape != (n, 3) or any(a.shape != (n,) for a in (su, rs, rc, pm)):
-        raise ValueError(f"X must be [{n},3] and the per-atom arrays [{n}]")
-    labels = np.zeros(int(n_res), np.uint32)
-    ties = np.zeros(n, np.uint8)
-    _check(lib.pesto_interface_labels(h, n, len(sizes), offs.ctypes.data, Xn.ctypes.data, su.ctypes.data, rs.ctypes.data, rc.ctypes.data,
-           pm.ctypes.data, int(n_res), float(r_thr), labels.ctypes.data, ties.ctypes.data, _lib.PTR_HOST, None))
+    side = _lib.Side(X, model._gpu)
+    X = side.put(X, np.float32, (n, 3), "X")
+    su = side.put(subunit, np.int32, (n,), "subunit")
+    rs = side.put(residue, np.int32, (n,), "residue")
+    rc = side.put(receptor, np.uint8, (n,), "receptor")
+    pm = side.put(partner_mask, np.uint32, (n,), "partner_mask")
+    labels = side.empty((int(n_res),), np.uint32)
+    ties = side.empty((n,), np.uint8)
+    lib = _lib.load()
+    _lib.check(lib.pesto_interface_labels(h, n, len(offs) - 1, offs.ctypes.data, side.ptr(X), side.ptr(su), side.ptr(rs), side.ptr(rc),
+                                          side.ptr(pm), int(n_res), float(r_thr), side.ptr(labels), side.ptr(ties), side.kind, side.stream),
+               lib.pesto_eval_last_error)
     return labels, ties
 
 
@@ -154,7 +122,7 @@ def interface_labels_batch(model, assemblies, r_thr=R_THR, l_types=L_TYPES, r_ty
         dev = torch.device("cuda", model._gpu)
         args = [torch.from_numpy(np.ascontiguousarray(a if a.dtype != np.uint32 else a.view(np.int32))).to(dev) for a in args]
     labels, ties = contact_labels(model, *args, [sizes[i] for i in keep], r_base, r_thr)
-    labels, ties = _host(labels).view(np.uint32), _host(ties)
+    labels, ties = _lib.host(labels).view(np.uint32), _lib.host(ties)
     bits = (labels[:, None] >> np.arange(len(r_types), dtype=np.uint32)[None, :]) & 1
     res_all = np.concatenate(rs)
     tie_res = np.zeros(r_base, bool)
@@ -179,44 +147,34 @@ def interface_labels(model, structure_or_subunits, r_thr=R_THR, l_types=L_TYPES,
 
 # ------------------------------------------------------------------ scores
 def bc_scores_batch(model, ys, ps):
-    """[S, 8, C] float32: bc_scoring of every (y [R_s, C], p [R_s, C]) pair in one launch (rows in BC_SCORE_NAMES order). ROCm tensors
-    stay on the GPU (result: a ROCm tensor); numpy / CPU tensors are staged (result: numpy, or a CPU tensor for CPU tensors)."""
+    """[S, 8, C] float32: bc_scoring of every (y [R_s, C], p [R_s, C]) pair in one launch (rows in BC_SCORE_NAMES order). ps[0] decides
+    where the call runs: ROCm tensors stay on the GPU (the other arrays are copied there where needed; result: a ROCm tensor); numpy / CPU
+    tensors are staged (result: numpy, or a CPU tensor for CPU tensors)."""
     if len(ys) != len(ps) or not ys:
         raise ValueError("ys and ps must be non-empty lists of the same length")
     h = model.handle
-    lib = _lib.load()
     shp = [tuple(p.shape) if len(p.shape) == 2 else (int(p.shape[0]), 1) for p in ps]
     C = shp[0][1]
     for y, s in zip(ys, shp):
         if s[1] != C or s[0] < 1 or int(y.shape[0]) != s[0] or (int(y.shape[1]) if len(y.shape) == 2 else 1) != C:
             raise ValueError("every y / p pair must be [R_s >= 1, C] with one C")
-    offs = np.zeros(len(ps) + 1, np.int32)
-    offs[1:] = np.cumsum([s[0] for s in shp])
+    offs = _lib.offsets([s[0] for s in shp])
     S = len(ps)
-    if _is_torch(ps[0]) and ps[0].is_cuda:
-        import torch
-        dev = ps[0].device
-        p = torch.cat([q.detach().reshape(s).to(torch.float32) for q, s in zip(ps, shp)]).contiguous()
-        y = torch.cat([(t if _is_torch(t) else torch.as_tensor(np.asarray(t))).to(dev).reshape(s) != 0 for t, s in zip(ys, shp)]).to(torch.uint8).contiguous()
-        out = torch.empty((S, 8, C), dtype=torch.float32, device=dev)
-        _check(lib.pesto_bc_scores(h, S, offs.ctypes.data, C, y.data_ptr(), p.data_ptr(), out.data_ptr(), _lib.PTR_DEVICE,
-               torch.cuda.current_stream(dev).cuda_stream))
-        return out
-    p = np.ascontiguousarray(np.concatenate([_host(q).reshape(s) for q, s in zip(ps, shp)]), dtype=np.float32)
-    y = np.ascontiguousarray(np.concatenate([_host(t).reshape(s) != 0 for t, s in zip(ys, shp)]), dtype=np.uint8)
-    out = np.empty((S, 8, C), np.float32)
-    _check(lib.pesto_bc_scores(h, S, offs.ctypes.data, C, y.ctypes.data, p.ctypes.data, out.ctypes.data, _lib.PTR_HOST, None))
-    if _is_torch(ps[0]):
-        import torch
-        return torch.from_numpy(out)
-    return out
+    side = _lib.Side(ps[0], model._gpu)
+    p = side.cat([q.reshape(s) for q, s in zip(ps, shp)], np.float32)
+    y = side.cat([t.reshape(s) != 0 for t, s in zip(ys, shp)], np.uint8)
+    out = side.empty((S, 8, C), np.float32)
+    lib = _lib.load()
+    _lib.check(lib.pesto_bc_scores(h, S, offs.ctypes.data, C, side.ptr(y), side.ptr(p), side.ptr(out), side.kind, side.stream),
+               lib.pesto_eval_last_error)
+    return side.result(out)
 
 
 def bc_scoring(y, p, model=None):
     """src/scoring.py:77-96: y [R, C] (0/1), p [R, C] probabilities -> [8, C] (acc, ppv, npv, tpr, tnr, mcc, auc, std). Without a model the
     call runs on a weightless handle of the tensors' GPU (GPU 0 for host arrays)."""
     if model is None:
-        model = _scoring_model(p.device.index if _is_torch(p) and p.is_cuda else 0)
+        model = _scoring_model(p.device.index if _lib.is_torch(p) and p.is_cuda else 0)
     return bc_scores_batch(model, [y], [p])[0]
 
 

@@ -9,8 +9,9 @@ Drop-in usage, as in apply_model.ipynb:73-93,155:
     z = model(X, ids_topk, q, M.float())          # fp32 [R, N2], same kind/device as the inputs
 
 All arithmetic runs in libpesto_hip.so on the MI355X; there is no PyTorch or CPU fallback. ``device`` only
-says where the caller's tensors live: CUDA(ROCm) tensors are consumed in place on torch's current stream,
-CPU tensors / numpy arrays are staged through the library's own buffers.
+says where the caller's tensors live. The lead argument of a call (X, X_frames, z, M) decides where its arrays go (_lib.Side): a
+CUDA(ROCm) lead is consumed in place on torch's current stream and the call's other arrays are copied to its GPU where they are not there
+already; with a CPU tensor / numpy lead every array is staged through the library's own buffers.
 
 ``precision`` (no reference counterpart - torch computes in fp32): "auto" (default) runs the state-update GEMMs as f16 hi/lo
 split MFMA and computes every STRUCTURE in which an activation left the f16 range again on the exact fp32 kernels (the other
@@ -31,10 +32,6 @@ from . import _lib
 from .config import normalise
 from .topology import mask_to_segments
 from .weights import blob_schema, flatten_state_dict, unflatten_blob
-
-
-def _is_torch(x):
-    return hasattr(x, "detach") and hasattr(x, "device")
 
 
 class Model:
@@ -71,7 +68,7 @@ class Model:
         """The weights as the flat float32 blob pesto_create takes (pesto_amd.weights.flatten_state_dict order: the reference's state_dict
         without m_nn / sdk) - what a rank receives when rank 0 broadcasts the model (sharding.broadcast_weights; SURVEY 8e: ncclBroadcast)."""
         from .weights import blob_size
-        b = np.ascontiguousarray(blob.detach().cpu().numpy() if _is_torch(blob) else blob, dtype=np.float32).ravel()
+        b = np.ascontiguousarray(_lib.host(blob), dtype=np.float32).ravel()
         if b.size != blob_size(self.config):
             raise ValueError(f"weight blob has {b.size} values, the configuration needs {blob_size(self.config)}")
         self._blob = b
@@ -268,21 +265,16 @@ class Model:
         """(res_of_atom, R) of the dense residue mask M [N,R]. A mask on the GPU is reduced there by k_mask_to_segments
         (pesto_mask_to_segments: one pass over M on torch's current stream, no host round trip, no ATen kernel); rows with != 1 member
         or an empty residue column poison the array, so the forward that consumes it reports PESTO_ERR_INVALID / NaN logits."""
-        if _is_torch(M) and M.is_cuda:
-            import torch
-            if M.device.index != self._gpu:
-                raise RuntimeError(f"inputs are on cuda:{M.device.index} but the model is on cuda:{self._gpu} (use .to())")
-            Mc = M.detach()
-            if Mc.dtype != torch.float32 or not Mc.is_contiguous():
-                Mc = Mc.to(torch.float32).contiguous()
+        if _lib.is_torch(M) and M.is_cuda:
+            side = _lib.Side(M, self._gpu)
+            Mc = side.put(M, np.float32)
             N, R = int(Mc.shape[0]), int(Mc.shape[1])
-            roa = torch.empty((N,), dtype=torch.int32, device=M.device)
-            stream = torch.cuda.current_stream(M.device).cuda_stream
-            _lib.check(_lib.load().pesto_mask_to_segments(self._ensure(), N, R, Mc.data_ptr(), roa.data_ptr(), _lib.PTR_DEVICE, stream))
+            roa = side.empty((N,), np.int32)
+            _lib.check(_lib.load().pesto_mask_to_segments(self._ensure(), N, R, side.ptr(Mc), side.ptr(roa), side.kind, side.stream))
             return roa, R
         if self.validate:
             return mask_to_segments(M)
-        Mn = M.detach().numpy() if _is_torch(M) else np.asarray(M)
+        Mn = _lib.host(M)
         return Mn.argmax(1).astype(np.int32), int(Mn.shape[1])
 
     def forward(self, X, ids_topk, q0, M):
@@ -295,67 +287,34 @@ class Model:
     def forward_segments(self, X, ids_topk, q0, res_of_atom, R, sizes=None):
         """Same as forward() with the residue mask given as res_of_atom [N] int32 (column index per atom).
         ``sizes``: atom counts of the structures the collated batch consists of - every structure then gets the result of its own
-        call (per-structure wrap-around target and max(D); pesto_forward_structures), as in the reference's bulk loops."""
+        call (per-structure wrap-around target and max(D); pesto_forward_structures), as in the reference's bulk loops.
+        X decides where the call runs (see the module docstring); z is of X's kind."""
         h = self._ensure()
-        lib = _lib.load()
-        n0 = self.config["em"]["N0"]
-        n_out = self.config["dm"]["N2"]
         offs = None
         if sizes is not None:
-            offs = np.zeros(len(sizes) + 1, dtype=np.int32)
-            offs[1:] = np.cumsum([int(v) for v in sizes])
+            offs = _lib.offsets(sizes)
             if int(offs[-1]) != int(X.shape[0]):
                 raise ValueError(f"sizes sum to {int(offs[-1])}, X has {int(X.shape[0])} atoms")
-
-        def call(N, k, xp, ip, kind, qp, rp, zp, ptr_kind, stream):
-            if offs is None:
-                return lib.pesto_forward(h, N, R, k, xp, ip, kind, qp, rp, zp, ptr_kind, stream)
-            return lib.pesto_forward_structures(h, N, R, k, len(offs) - 1, offs.ctypes.data, xp, ip, kind, qp, rp, zp, ptr_kind, stream)
-
-        if _is_torch(X) and X.is_cuda:
-            import torch
-            if X.device.index != self._gpu:
-                raise RuntimeError(f"inputs are on cuda:{X.device.index} but the model is on cuda:{self._gpu} (use .to())")
-            Xc = X.detach().to(torch.float32).contiguous()
-            ids = ids_topk.detach()
-            if ids.dtype not in (torch.int32, torch.int64):
-                ids = ids.to(torch.int64)
-            ids = ids.contiguous()
-            qc = q0.detach().to(torch.float32).contiguous()
-            roa = res_of_atom if _is_torch(res_of_atom) else torch.as_tensor(np.asarray(res_of_atom), device=X.device)
-            roa = roa.to(device=X.device, dtype=torch.int32).contiguous()
-            N, k = ids.shape
-            self._check_shapes(N, Xc.shape, qc.shape, roa.shape, n0)
-            z = torch.empty((R, n_out), dtype=torch.float32, device=X.device)
-            stream = torch.cuda.current_stream(X.device).cuda_stream
-            _lib.check(call(N, k, Xc.data_ptr(), ids.data_ptr(), _lib.IDS_INT64 if ids.dtype == torch.int64 else _lib.IDS_INT32,
-                            qc.data_ptr(), roa.data_ptr(), z.data_ptr(), _lib.PTR_DEVICE, stream))
+        side = _lib.Side(X, self._gpu)
+        ids = side.put(ids_topk, (np.int64, np.int32))
+        N, k = ids.shape
+        X = side.put(X, np.float32, (N, 3), "X")
+        q = side.put(q0, np.float32, (N, self.config["em"]["N0"]), "q0")
+        roa = side.put(res_of_atom, np.int32, (N,), "res_of_atom")
+        z = side.empty((R, self.config["dm"]["N2"]), np.float32)
+        args = (side.ptr(X), side.ptr(ids), _lib.ids_kind(ids), side.ptr(q), side.ptr(roa), side.ptr(z), side.kind, side.stream)
+        lib = _lib.load()
+        if offs is None:
+            _lib.check(lib.pesto_forward(h, N, R, k, *args))
+        else:
+            _lib.check(lib.pesto_forward_structures(h, N, R, k, len(offs) - 1, offs.ctypes.data, *args))
+        if side.device is not None:
             # precision "auto": checked before the call returned (z is final). async_auto: the check is made by the NEXT call on the handle
-            # (or synchronize()), which may repeat flagged structures on the fp32 kernels into the same z - the launch's buffers stay
-            # referenced until then.
-            self._last_device_call = (Xc, ids, qc, roa, z) if self.async_auto else None
-            self._tick_auto_bill()
-            return z
-        # host path: CPU torch tensors or numpy arrays
-        as_torch = _is_torch(X)
-        Xn = np.ascontiguousarray(X.detach().numpy() if as_torch else X, dtype=np.float32)
-        idn = ids_topk.detach().numpy() if _is_torch(ids_topk) else np.asarray(ids_topk)
-        if idn.dtype not in (np.int32, np.int64):
-            idn = idn.astype(np.int64)
-        idn = np.ascontiguousarray(idn)
-        qn = np.ascontiguousarray(q0.detach().numpy() if _is_torch(q0) else q0, dtype=np.float32)
-        roa = np.ascontiguousarray(res_of_atom.detach().cpu().numpy() if _is_torch(res_of_atom) else res_of_atom, dtype=np.int32)
-        N, k = idn.shape
-        self._check_shapes(N, Xn.shape, qn.shape, roa.shape, n0)
-        z = np.empty((R, n_out), dtype=np.float32)
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _lib.check(call(N, k, p(Xn), p(idn), _lib.IDS_INT64 if idn.dtype == np.int64 else _lib.IDS_INT32,
-                        p(qn), p(roa), p(z), _lib.PTR_HOST, None))
+            # (or synchronize()), which may repeat flagged structures on the fp32 kernels into the same z - the launch's buffers (put()'s
+            # copies included) stay referenced until then.
+            self._last_device_call = (X, ids, q, roa, z) if self.async_auto else None
         self._tick_auto_bill()
-        if as_torch:
-            import torch
-            return torch.from_numpy(z)
-        return z
+        return side.result(z)
 
     @staticmethod
     def _check_shapes(N, xs, qs, rs, n0):
@@ -386,19 +345,19 @@ class Model:
         Xp, Ip, Qp, Ap, Zp = (arr(ctypes.c_void_p) for _ in range(5))
         kind = None
         for b, (X, ids, q0, M) in enumerate(structures):
-            Mh = M.detach().cpu().numpy() if _is_torch(M) else np.asarray(M)
+            Mh = _lib.host(M)
             if Mh.ndim == 1:                      # the compact forms forward_batch_submit takes: res_of_atom [N] and uint8 feature indices
                 roa, R = Mh.astype(np.int32), (int(Mh.max()) + 1 if Mh.size else 0)
             else:
                 roa, R = mask_to_segments(Mh) if self.validate else (Mh.argmax(1).astype(np.int32), int(Mh.shape[1]))
-            Xn = np.ascontiguousarray(X.detach().cpu().numpy() if _is_torch(X) else X, dtype=np.float32)
-            idn = ids.detach().cpu().numpy() if _is_torch(ids) else np.asarray(ids)
+            Xn = np.ascontiguousarray(_lib.host(X), dtype=np.float32)
+            idn = _lib.host(ids)
             idn = np.ascontiguousarray(idn.astype(np.int32) if idn.dtype != np.int64 else idn)
             if kind is None:
                 kind = idn.dtype
             elif idn.dtype != kind:
                 idn = np.ascontiguousarray(idn.astype(kind))
-            qh = q0.detach().cpu().numpy() if _is_torch(q0) else np.asarray(q0)
+            qh = _lib.host(q0)
             if qh.dtype == np.uint8:              # indices -> the dense one-hot rows this (synchronous) entry point uploads
                 offs = self.ONEHOT_OFFSETS[n0]
                 dense = np.zeros((qh.shape[0], n0), np.float32)
@@ -406,7 +365,7 @@ class Model:
                     dense[np.arange(qh.shape[0]), o + qh[:, c].astype(np.int64)] = 1.0
                 qh = dense
             qn = np.ascontiguousarray(qh, dtype=np.float32)
-            roa = np.ascontiguousarray(roa.detach().cpu().numpy() if _is_torch(roa) else roa, dtype=np.int32)
+            roa = np.ascontiguousarray(_lib.host(roa), dtype=np.int32)
             N = Xn.shape[0]
             if idn.ndim != 2 or idn.shape[0] != N:
                 raise ValueError(f"structure {b}: ids_topk must be [N, k] with N={N}")
@@ -445,8 +404,7 @@ class Model:
         Np, Rp, kp = arr(ctypes.c_int64), arr(ctypes.c_int64), arr(ctypes.c_int32)
         Xp, Ip, Qp, Jp, Ap, Zp = (arr(ctypes.c_void_p) for _ in range(6))
         zs, keep = [], []
-        host = lambda a: a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
-        qhs = [host(s[2]) for s in structures]            # (one device-to-host copy per structure when q lives on the GPU - ADVICE r4)
+        qhs = [_lib.host(s[2]) for s in structures]            # (one device-to-host copy per structure when q lives on the GPU - ADVICE r4)
         n_idx_given = sum(1 for qh in qhs if qh.dtype == np.uint8)
         if n_idx_given not in (0, nb):
             raise ValueError("either every structure passes q as uint8 indices or none does")
@@ -458,7 +416,7 @@ class Model:
         # copy (PESTO_IDS_NARROW), the one-hot rows are found while they are packed. No numpy pass touches an element here.
         ids_kinds = set()
         for b, (X, ids, q0, M) in enumerate(structures):
-            Mh = host(M)
+            Mh = _lib.host(M)
             if Mh.ndim == 1:                        # res_of_atom given: the library checks its range, the forward that every residue has an atom
                 roa = np.ascontiguousarray(Mh, dtype=np.int32)
                 R = int(roa.max()) + 1 if roa.size else 0
@@ -467,8 +425,8 @@ class Model:
                 # skip the check to save four numpy passes)
                 roa, R = mask_to_segments(Mh)
                 roa = np.ascontiguousarray(roa, dtype=np.int32)
-            Xn = np.ascontiguousarray(host(X), dtype=np.float32)
-            idr = host(ids)
+            Xn = np.ascontiguousarray(_lib.host(X), dtype=np.float32)
+            idr = _lib.host(ids)
             if idr.dtype not in (np.int32, np.int64, np.uint16):
                 idr = idr.astype(np.int32)
             if idr.dtype == np.uint16 and not compact:
@@ -536,70 +494,33 @@ class Model:
 
     def forward_frames_segments(self, X_frames, ids_topk, q0, res_of_atom, R, frame_axis=0, frames_per_launch=0):
         h = self._ensure()
-        lib = _lib.load()
-        n0 = self.config["em"]["N0"]
-        n_out = self.config["dm"]["N2"]
         if frame_axis not in (0, 1) or len(X_frames.shape) != 3 or X_frames.shape[2] != 3:
             raise ValueError("X_frames must be [F,N,3] (frame_axis=0) or [N,F,3] (frame_axis=1)")
         F, N = (X_frames.shape[0], X_frames.shape[1]) if frame_axis == 0 else (X_frames.shape[1], X_frames.shape[0])
-        if _is_torch(X_frames) and X_frames.is_cuda:
-            import torch
-            dev = X_frames.device
-            if dev.index != self._gpu:
-                raise RuntimeError(f"inputs are on cuda:{dev.index} but the model is on cuda:{self._gpu} (use .to())")
-            Xc = X_frames.detach()
-            if Xc.dtype != torch.float32 or Xc.stride(2) != 1:
-                Xc = Xc.to(torch.float32).contiguous()
-            fs, as_ = (Xc.stride(0), Xc.stride(1)) if frame_axis == 0 else (Xc.stride(1), Xc.stride(0))
-            ids = ids_topk.detach()
-            if ids.dtype not in (torch.int32, torch.int64):
-                ids = ids.to(torch.int64)
-            ids = ids.to(dev).contiguous()
-            qc = q0.detach().to(device=dev, dtype=torch.float32).contiguous()
-            roa = res_of_atom if _is_torch(res_of_atom) else torch.as_tensor(np.asarray(res_of_atom))
-            roa = roa.to(device=dev, dtype=torch.int32).contiguous()
-            if ids.shape[0] != N:
-                raise ValueError(f"ids_topk has {ids.shape[0]} rows, frames have {N} atoms")
-            self._check_shapes(N, (N, 3), qc.shape, roa.shape, n0)
-            z = torch.empty((F, R, n_out), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.pesto_forward_frames(h, N, R, ids.shape[1], F, Xc.data_ptr(), fs, as_, ids.data_ptr(),
-                                                _lib.IDS_INT64 if ids.dtype == torch.int64 else _lib.IDS_INT32, qc.data_ptr(),
-                                                roa.data_ptr(), z.data_ptr(), frames_per_launch, _lib.PTR_DEVICE, stream))
-            self._last_device_call = (Xc, ids, qc, roa, z) if self.async_auto else None      # (as in forward_segments)
-            return z
-        as_torch = _is_torch(X_frames)
-        Xn = np.asarray(X_frames.detach().numpy() if as_torch else X_frames)
-        if Xn.dtype != np.float32 or Xn.strides[2] != 4 or Xn.strides[0] % 4 or Xn.strides[1] % 4:
-            Xn = np.ascontiguousarray(Xn, dtype=np.float32)
-        fs, as_ = (Xn.strides[0] // 4, Xn.strides[1] // 4) if frame_axis == 0 else (Xn.strides[1] // 4, Xn.strides[0] // 4)
-        idn = ids_topk.detach().numpy() if _is_torch(ids_topk) else np.asarray(ids_topk)
-        if idn.dtype not in (np.int32, np.int64):
-            idn = idn.astype(np.int64)
-        idn = np.ascontiguousarray(idn)
-        qn = np.ascontiguousarray(q0.detach().numpy() if _is_torch(q0) else q0, dtype=np.float32)
-        roa = np.ascontiguousarray(res_of_atom.detach().cpu().numpy() if _is_torch(res_of_atom) else res_of_atom, dtype=np.int32)
-        if idn.shape[0] != N:
-            raise ValueError(f"ids_topk has {idn.shape[0]} rows, frames have {N} atoms")
-        self._check_shapes(N, (N, 3), qn.shape, roa.shape, n0)
-        z = np.empty((F, R, n_out), dtype=np.float32)
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _lib.check(lib.pesto_forward_frames(h, N, R, idn.shape[1], F, p(Xn), fs, as_, p(idn),
-                                            _lib.IDS_INT64 if idn.dtype == np.int64 else _lib.IDS_INT32, p(qn), p(roa), p(z),
-                                            frames_per_launch, _lib.PTR_HOST, None))
-        if as_torch:
-            import torch
-            return torch.from_numpy(z)
-        return z
+        side = _lib.Side(X_frames, self._gpu)
+        Xf = side.put(X_frames, np.float32, strided=True)
+        st = _lib.strides(Xf)
+        fs, as_ = (st[0], st[1]) if frame_axis == 0 else (st[1], st[0])
+        ids = side.put(ids_topk, (np.int64, np.int32))
+        if ids.shape[0] != N:
+            raise ValueError(f"ids_topk has {ids.shape[0]} rows, frames have {N} atoms")
+        q = side.put(q0, np.float32, (N, self.config["em"]["N0"]), "q0")
+        roa = side.put(res_of_atom, np.int32, (N,), "res_of_atom")
+        z = side.empty((F, R, self.config["dm"]["N2"]), np.float32)
+        lib = _lib.load()
+        _lib.check(lib.pesto_forward_frames(h, N, R, ids.shape[1], F, side.ptr(Xf), fs, as_, side.ptr(ids), _lib.ids_kind(ids), side.ptr(q),
+                                            side.ptr(roa), side.ptr(z), frames_per_launch, side.kind, side.stream))
+        if side.device is not None:
+            self._last_device_call = (Xf, ids, q, roa, z) if self.async_auto else None      # (as in forward_segments)
+        return side.result(z)
 
     # ------------------------------------------------------------------ post-processing on the GPU
     def postprocess(self, z, M_or_res_of_atom=None):
         """(p, bfactor): p = sigmoid(z) [R, N2] (apply_model.ipynb:160) and, when the residue mask M [N,R] (or res_of_atom [N]) is
         given, bfactor [N2, N] with bfactor[c][i] = p[residue of atom i][c] - encode_bfactor's per-residue branch
-        (src/structure.py:208-218) for every output channel at once. ROCm tensors stay on the GPU (asynchronous)."""
+        (src/structure.py:208-218) for every output channel at once. z decides where the call runs: ROCm tensors stay on the GPU
+        (asynchronous); the results are of z's kind."""
         h = self._ensure()
-        lib = _lib.load()
-        n_out = self.config["dm"]["N2"]
         R = int(z.shape[0])
         roa = None
         if M_or_res_of_atom is not None:
@@ -610,35 +531,15 @@ class Model:
                 roa = m.argmax(1)
             else:
                 roa = m
-        if _is_torch(z) and z.is_cuda:
-            import torch
-            zc = z.detach().to(torch.float32).contiguous()
-            p = torch.empty_like(zc)
-            bf, rp, N = None, 0, 1
-            if roa is not None:
-                roa = (roa if _is_torch(roa) else torch.as_tensor(np.asarray(roa))).to(device=z.device, dtype=torch.int32).contiguous()
-                N = int(roa.shape[0])
-                bf = torch.empty((n_out, N), dtype=torch.float32, device=z.device)
-                rp = roa.data_ptr()
-            stream = torch.cuda.current_stream(z.device).cuda_stream
-            _lib.check(lib.pesto_postprocess(h, N, R, zc.data_ptr(), rp, p.data_ptr(), bf.data_ptr() if bf is not None else 0,
-                                             _lib.PTR_DEVICE, stream))
-            return p, bf
-        as_torch = _is_torch(z)
-        zn = np.ascontiguousarray(z.detach().numpy() if as_torch else z, dtype=np.float32)
-        p = np.empty_like(zn)
-        bf, N, rp = None, 1, None
-        if roa is not None:
-            roa = np.ascontiguousarray(roa.detach().cpu().numpy() if _is_torch(roa) else roa, dtype=np.int32)
-            N = int(roa.shape[0])
-            bf = np.empty((n_out, N), dtype=np.float32)
-            rp = roa.ctypes.data_as(ctypes.c_void_p)
-        _lib.check(lib.pesto_postprocess(h, N, R, zn.ctypes.data_as(ctypes.c_void_p), rp, p.ctypes.data_as(ctypes.c_void_p),
-                                         bf.ctypes.data_as(ctypes.c_void_p) if bf is not None else None, _lib.PTR_HOST, None))
-        if as_torch:
-            import torch
-            return torch.from_numpy(p), (torch.from_numpy(bf) if bf is not None else None)
-        return p, bf
+        side = _lib.Side(z, self._gpu)
+        zc = side.put(z, np.float32)
+        roa = None if roa is None else side.put(roa, np.int32)
+        N = 1 if roa is None else int(roa.shape[0])
+        p = side.empty(tuple(zc.shape), np.float32)
+        bf = None if roa is None else side.empty((self.config["dm"]["N2"], N), np.float32)
+        lib = _lib.load()
+        _lib.check(lib.pesto_postprocess(h, N, R, side.ptr(zc), side.ptr(roa), side.ptr(p), side.ptr(bf), side.kind, side.stream))
+        return side.result(p), side.result(bf)
 
     # ------------------------------------------------------------------ k-NN topology + collate on the GPU
     def knn_collate(self, X, sizes, k=64):
@@ -647,63 +548,31 @@ class Model:
         exact k nearest neighbours within each structure, ascending distance, D < 1e-2 entries last, 1-based batch-global ids,
         0 = padding. X: [sum(sizes), 3] float32 (ROCm tensor -> int64 ROCm tensor on the current stream; CPU tensor / numpy -> same kind)."""
         h = self._ensure()
-        lib = _lib.load()
-        sizes = [int(v) for v in sizes]
-        offs = np.zeros(len(sizes) + 1, dtype=np.int32)
-        offs[1:] = np.cumsum(sizes)
+        offs = _lib.offsets(sizes)
         n = int(offs[-1])
-        if _is_torch(X) and X.is_cuda:
-            import torch
-            Xc = X.detach().to(torch.float32).contiguous()
-            if tuple(Xc.shape) != (n, 3):
-                raise ValueError(f"X must be [{n},3], got {tuple(Xc.shape)}")
-            ids = torch.empty((n, 64), dtype=torch.int64, device=X.device)
-            stream = torch.cuda.current_stream(X.device).cuda_stream
-            _lib.check(lib.pesto_knn_collate(h, n, len(sizes), offs.ctypes.data, Xc.data_ptr(), k, ids.data_ptr(), _lib.IDS_INT64,
-                                             _lib.PTR_DEVICE, stream))
-            return ids
-        as_torch = _is_torch(X)
-        Xn = np.ascontiguousarray(X.detach().numpy() if as_torch else X, dtype=np.float32)
-        if Xn.shape != (n, 3):
-            raise ValueError(f"X must be [{n},3], got {Xn.shape}")
-        ids = np.empty((n, 64), dtype=np.int64)
-        _lib.check(lib.pesto_knn_collate(h, n, len(sizes), offs.ctypes.data, Xn.ctypes.data, k, ids.ctypes.data, _lib.IDS_INT64,
-                                         _lib.PTR_HOST, None))
-        if as_torch:
-            import torch
-            return torch.from_numpy(ids)
-        return ids
+        side = _lib.Side(X, self._gpu)
+        X = side.put(X, np.float32, (n, 3), "X")
+        ids = side.empty((n, 64), np.int64)
+        lib = _lib.load()
+        _lib.check(lib.pesto_knn_collate(h, n, len(offs) - 1, offs.ctypes.data, side.ptr(X), k, side.ptr(ids), _lib.IDS_INT64, side.kind,
+                                         side.stream))
+        return side.result(ids)
 
     def knn_tie_rows(self, X, sizes, ids_topk, k=64):
         """uint8 [sum(sizes)]: bit 0 / 1 / 2 / 3 set where an exact float32 distance tie of that row straddles the cut after column
         8 / 16 / 32 / 64 of ``ids_topk`` (the table of knn_collate for the same X / sizes) - the rows on which the reference's torch.topk
-        may have picked the other of two equally distant atoms for a layer's neighbourhood (pesto_knn_tie_rows). numpy in, numpy out."""
+        may have picked the other of two equally distant atoms for a layer's neighbourhood (pesto_knn_tie_rows). X decides where the
+        call runs: a ROCm X gives a uint8 ROCm tensor on the current stream (ids_topk is copied to its GPU where needed), host X numpy."""
         h = self._ensure()
-        lib = _lib.load()
-        sizes = [int(v) for v in sizes]
-        offs = np.zeros(len(sizes) + 1, dtype=np.int32)
-        offs[1:] = np.cumsum(sizes)
+        offs = _lib.offsets(sizes)
         n = int(offs[-1])
-        if _is_torch(X) and X.is_cuda:                # ROCm tensors: uint8 ROCm tensor on the current stream
-            import torch
-            Xc = X.detach().to(torch.float32).contiguous()
-            idc = ids_topk.detach()
-            idc = (idc if idc.dtype in (torch.int32, torch.int64) else idc.to(torch.int64)).contiguous()
-            if tuple(Xc.shape) != (n, 3) or tuple(idc.shape) != (n, 64):
-                raise ValueError(f"X must be [{n},3] and ids_topk [{n},64]")
-            fl = torch.empty((n,), dtype=torch.uint8, device=X.device)
-            _lib.check(lib.pesto_knn_tie_rows(h, n, len(sizes), offs.ctypes.data, Xc.data_ptr(), k, idc.data_ptr(),
-                                              _lib.IDS_INT64 if idc.dtype == torch.int64 else _lib.IDS_INT32, fl.data_ptr(), _lib.PTR_DEVICE,
-                                              torch.cuda.current_stream(X.device).cuda_stream))
-            return fl
-        Xn = np.ascontiguousarray(X.detach().cpu().numpy() if _is_torch(X) else X, dtype=np.float32)
-        idn = ids_topk.detach().cpu().numpy() if _is_torch(ids_topk) else np.asarray(ids_topk)
-        idn = np.ascontiguousarray(idn if idn.dtype in (np.int32, np.int64) else idn.astype(np.int64))
-        if Xn.shape != (n, 3) or idn.shape != (n, 64):
-            raise ValueError(f"X must be [{n},3] and ids_topk [{n},64]")
-        flags = np.zeros(n, np.uint8)
-        _lib.check(lib.pesto_knn_tie_rows(h, n, len(sizes), offs.ctypes.data, Xn.ctypes.data, k, idn.ctypes.data,
-                                          _lib.IDS_INT64 if idn.dtype == np.int64 else _lib.IDS_INT32, flags.ctypes.data, _lib.PTR_HOST, None))
+        side = _lib.Side(X, self._gpu)
+        X = side.put(X, np.float32, (n, 3), "X")
+        ids = side.put(ids_topk, (np.int64, np.int32), (n, 64), "ids_topk")
+        flags = side.empty((n,), np.uint8)
+        lib = _lib.load()
+        _lib.check(lib.pesto_knn_tie_rows(h, n, len(offs) - 1, offs.ctypes.data, side.ptr(X), k, side.ptr(ids), _lib.ids_kind(ids),
+                                          side.ptr(flags), side.kind, side.stream))
         return flags
 
     # ------------------------------------------------------------------ per-stage access (tests)

@@ -28,22 +28,6 @@ MAX_SEL = 1024
 FORCE_LARGE = 1         # PESTO_PATCHES_FORCE_LARGE
 
 
-def _is_torch(x):
-    return hasattr(x, "detach") and hasattr(x, "device")
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
-
-
-def _check(rc):
-    if rc != 0:
-        msg = _lib.load().pesto_patches_last_error()
-        err = _lib.PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")
-        err.code = rc
-        raise err
-
-
 def selections(n_labels=len(LABELS), pairs=True):
     """The reference's loop order: (i, i) for i < n (pairs=False), or (i, j) for i = 0..n-1, j = i..n-1 (pairs=True)."""
     if pairs:
@@ -92,8 +76,9 @@ def patch_labels(model, ps, xyzs, afss=None, has_ca=None, sel=None, afs_thr=AFS_
     """pesto_interface_patches on a batch: returns (patch_of [n_sel, R] int32, n_patches [S, n_sel] int32, patch_size [n_sel, R] int32,
     patch_mean [n_sel, R, 2] float32, offsets [S + 1] numpy) with R the rows of all structures (structure s: rows offsets[s]:offsets[s+1]).
     patch_of: the patch number within (structure, selection), -1 off the nodes; size and mean (of p[:, i], p[:, j]) at each patch's
-    smallest member row. sel: [(i, j)] (default: every pair of the classes). ROCm tensors run on the device buffers (device pointers,
-    torch's current stream; the results are ROCm tensors); numpy arrays / CPU tensors are staged (numpy results)."""
+    smallest member row. sel: [(i, j)] (default: every pair of the classes). ps[0] decides where the call runs: ROCm tensors run on the
+    device buffers (device pointers, torch's current stream; the other arrays are copied to its GPU where needed; the results are ROCm
+    tensors); numpy arrays / CPU tensors are staged (numpy results)."""
     n_class = int(ps[0].shape[1]) if ps and len(ps[0].shape) == 2 else 0
     sel = selections(n_class, True) if sel is None else [tuple(int(v) for v in ij) for ij in sel]
     C, sizes = _validate(ps, xyzs, afss, has_ca, len(sel), d_thr)
@@ -107,43 +92,25 @@ def patch_labels(model, ps, xyzs, afss=None, has_ca=None, sel=None, afs_thr=AFS_
             has_ca = [np.ones(n, np.uint8) if h is None else h for h, n in zip(has_ca, sizes)]
         else:
             has_ca = None
-    offs = np.zeros(len(ps) + 1, np.int32)
-    offs[1:] = np.cumsum(sizes)
+    offs = _lib.offsets(sizes)
     R, S, K = int(offs[-1]), len(ps), len(sel)
     if R * max(C, K) >= 2 ** 31:
         raise ValueError(f"too many rows ({R}) for {C} classes and {K} selections")
     sel_a = np.ascontiguousarray(np.asarray(sel, np.int32).reshape(K, 2))
     h = model.handle
+    side = _lib.Side(ps[0], model._gpu)
+    p = side.cat(ps, np.float32)
+    x = side.cat(xyzs, np.float32)
+    a = side.cat(afss, np.float32) if afss is not None else None
+    c = side.cat([q != 0 for q in has_ca], np.uint8) if has_ca is not None else None
+    po, psz = side.empty((K, R), np.int32), side.empty((K, R), np.int32)
+    npch = side.empty((S, K), np.int32)
+    pm = side.empty((K, R, 2), np.float32)
     lib = _lib.load()
-    flags = FORCE_LARGE if force_large else 0
-    if _is_torch(ps[0]) and ps[0].is_cuda:
-        import torch
-        dev = ps[0].device
-        t = lambda a, dt: (a if _is_torch(a) else torch.as_tensor(np.asarray(a))).detach().to(device=dev, dtype=dt)
-        p = torch.cat([t(q, torch.float32) for q in ps]).contiguous()
-        x = torch.cat([t(q, torch.float32) for q in xyzs]).contiguous()
-        a = torch.cat([t(q, torch.float32) for q in afss]).contiguous() if afss is not None else None
-        c = torch.cat([t(q, torch.bool).to(torch.uint8) for q in has_ca]).contiguous() if has_ca is not None else None
-        po = torch.empty((K, R), dtype=torch.int32, device=dev)
-        npch = torch.empty((S, K), dtype=torch.int32, device=dev)
-        psz = torch.empty((K, R), dtype=torch.int32, device=dev)
-        pm = torch.empty((K, R, 2), dtype=torch.float32, device=dev)
-        _check(lib.pesto_interface_patches(h, S, offs.ctypes.data, C, x.data_ptr(), p.data_ptr(), a.data_ptr() if a is not None else None,
-               c.data_ptr() if c is not None else None, K, sel_a.ctypes.data, float(afs_thr), float(p_thr), float(d_thr), po.data_ptr(),
-               npch.data_ptr(), psz.data_ptr(), pm.data_ptr(), flags, _lib.PTR_DEVICE, torch.cuda.current_stream(dev).cuda_stream))
-        return po, npch, psz, pm, offs
-    cat = lambda arrs, dt: np.ascontiguousarray(np.concatenate([_host(q) for q in arrs]), dtype=dt)
-    p = cat(ps, np.float32)
-    x = cat(xyzs, np.float32)
-    a = cat(afss, np.float32) if afss is not None else None
-    c = np.ascontiguousarray(np.concatenate([_host(q) != 0 for q in has_ca]), dtype=np.uint8) if has_ca is not None else None
-    po = np.empty((K, R), np.int32)
-    npch = np.empty((S, K), np.int32)
-    psz = np.empty((K, R), np.int32)
-    pm = np.empty((K, R, 2), np.float32)
-    _check(lib.pesto_interface_patches(h, S, offs.ctypes.data, C, x.ctypes.data, p.ctypes.data, a.ctypes.data if a is not None else None,
-           c.ctypes.data if c is not None else None, K, sel_a.ctypes.data, float(afs_thr), float(p_thr), float(d_thr), po.ctypes.data,
-           npch.ctypes.data, psz.ctypes.data, pm.ctypes.data, flags, _lib.PTR_HOST, None))
+    _lib.check(lib.pesto_interface_patches(h, S, offs.ctypes.data, C, side.ptr(x), side.ptr(p), side.ptr(a), side.ptr(c), K, sel_a.ctypes.data,
+                                           float(afs_thr), float(p_thr), float(d_thr), side.ptr(po), side.ptr(npch), side.ptr(psz),
+                                           side.ptr(pm), FORCE_LARGE if force_large else 0, side.kind, side.stream),
+               lib.pesto_patches_last_error)
     return po, npch, psz, pm, offs
 
 
@@ -180,7 +147,7 @@ def interface_patches_batch(model, ps, xyzs, afss=None, has_ca=None, pairs=True,
     if ps and len(ps[0].shape) == 2 and int(ps[0].shape[1]) < len(labels):
         raise ValueError(f"p has {int(ps[0].shape[1])} classes, {len(labels)} labels need at least as many")
     po, npch, psz, pm, offs = patch_labels(model, ps, xyzs, afss, has_ca, sel, afs_thr, p_thr, d_thr, force_large)
-    po, npch, psz, pm = _host(po), _host(npch), _host(psz), _host(pm)
+    po, npch, psz, pm = (_lib.host(v) for v in (po, npch, psz, pm))
     lists, stats = _lists(po, npch, psz, pm, offs, return_stats)
     if pairs:
         keys = selection_keys(labels, True)
@@ -200,7 +167,7 @@ def interface_patches(p, xyz, afs=None, has_ca=None, model=None, pairs=True, afs
     """interface_patches_batch for ONE structure (the reference's cluster_interfaces(entry, ...) with pairs=False, cluster_multi_interfaces
     with pairs=True). Without a model the call runs on a weightless handle of p's GPU (GPU 0 for host arrays)."""
     if model is None:
-        model = _default_model(p.device.index if _is_torch(p) and p.is_cuda else 0)
+        model = _default_model(p.device.index if _lib.is_torch(p) and p.is_cuda else 0)
     r = interface_patches_batch(model, [p], [xyz], None if afs is None else [afs], None if has_ca is None else [has_ca], pairs, afs_thr,
                                 p_thr, d_thr, labels, return_stats, force_large)
     return (r[0][0], r[1][0]) if return_stats else r[0]

@@ -16,16 +16,12 @@ Everything here is numpy (torch tensors are accepted and returned where given).
 """
 import numpy as np
 
+from ._lib import host
+
 try:  # scipy is present in the image; only needed for N > 4096
     from scipy.spatial import cKDTree
 except Exception:  # pragma: no cover
     cKDTree = None
-
-
-def _np(a):
-    if hasattr(a, "detach"):
-        return a.detach().cpu().numpy()
-    return np.asarray(a)
 
 
 def _like(ref, a):
@@ -103,7 +99,7 @@ def extract_topology(X, num_nn=64):
 
     Only the index tensor is returned (the reference also returns D/R, which callers discard:
     apply_model.ipynb:149, profiling.py:92)."""
-    Xn = np.ascontiguousarray(_np(X), dtype=np.float32)
+    Xn = np.ascontiguousarray(host(X), dtype=np.float32)
     n = Xn.shape[0]
     knn = min(num_nn, n)
     if n <= 4096 or cKDTree is None:
@@ -119,16 +115,16 @@ def collate_batch_features(batch_data, max_num_nn=64):
     (src/dataset.py:91-112): ids become 1-based with a per-structure offset, zero-padded to
     ``max_num_nn`` columns (0 = sink); M is block-diagonal float32."""
     ref = batch_data[0][0]
-    Xs = [np.asarray(_np(d[0]), dtype=np.float32) for d in batch_data]
-    qs = [np.asarray(_np(d[2]), dtype=np.float32) for d in batch_data]
+    Xs = [np.asarray(host(d[0]), dtype=np.float32) for d in batch_data]
+    qs = [np.asarray(host(d[2]), dtype=np.float32) for d in batch_data]
     n_tot = sum(x.shape[0] for x in Xs)
-    r_tot = sum(_np(d[3]).shape[1] for d in batch_data)
+    r_tot = sum(host(d[3]).shape[1] for d in batch_data)
     ids_topk = np.zeros((n_tot, max_num_nn), dtype=np.int64)
     M = np.zeros((n_tot, r_tot), dtype=np.float32)
     ix0 = iy0 = 0
     for d in batch_data:
-        ids = _np(d[1]).astype(np.int64)
-        Mi = _np(d[3])
+        ids = host(d[1]).astype(np.int64)
+        Mi = host(d[3])
         n, r = Mi.shape
         if ids.shape[1] > max_num_nn:
             raise ValueError("more neighbour columns than max_num_nn")
@@ -152,7 +148,7 @@ def mask_to_segments(M):
         if not bool(Mb.any(0).all()):
             raise ValueError("M: empty residue column")
         return torch.argmax(Mb.to(torch.int8), dim=1).to(torch.int32), int(M.shape[1])
-    Mh = _np(M)
+    Mh = host(M)
     if Mh.ndim == 2 and Mh.dtype in (np.float32, np.bool_, np.uint8) and Mh.flags.c_contiguous and Mh.size:
         # one native pass over the rows (libpesto_io.so, host only) instead of four numpy passes over the dense mask: this reduction is
         # the largest host cost per structure of the bulk path when callers hand over the reference's dense M (profiles/r04_host_packing.json)

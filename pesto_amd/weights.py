@@ -10,6 +10,7 @@ language; tests/test_weights.py checks they agree through pesto_blob_size()).
 """
 import numpy as np
 
+from ._lib import host
 from .config import normalise
 
 
@@ -50,12 +51,6 @@ def blob_size(config):
     return int(sum(int(np.prod(shape)) for _, shape in blob_schema(config)))
 
 
-def _to_numpy(v):
-    if hasattr(v, "detach"):
-        v = v.detach().cpu().numpy()
-    return np.asarray(v)
-
-
 def flatten_state_dict(config, state_dict, strict=True):
     """state_dict (torch tensors or numpy arrays, reference key names) -> flat float32 blob.
 
@@ -68,19 +63,19 @@ def flatten_state_dict(config, state_dict, strict=True):
     for key, shape in blob_schema(c):
         if key not in state_dict:
             raise KeyError(f"missing key in state_dict: {key}")
-        a = _to_numpy(state_dict[key])
+        a = host(state_dict[key])
         if tuple(a.shape) != tuple(shape):
             raise ValueError(f"size mismatch for {key}: got {tuple(a.shape)}, expected {tuple(shape)}")
         parts.append(np.ascontiguousarray(a, dtype=np.float32).ravel())
     for li, l in enumerate(c["sum"]):
         k = f"sum.{li}.m_nn"
         if k in state_dict:
-            m = _to_numpy(state_dict[k])
+            m = host(state_dict[k])
             if m.shape != (l["nn"],) or not np.array_equal(m, np.arange(l["nn"])):
                 raise ValueError(f"{k} must be arange({l['nn']}) (model_operations.py:223)")
         k = f"sum.{li}.su.sdk"
         if k in state_dict:
-            sdk = float(_to_numpy(state_dict[k]))
+            sdk = float(host(state_dict[k]))
             if abs(sdk - float(np.sqrt(np.float32(l["Nk"])))) > 1e-6:
                 raise ValueError(f"{k} must be sqrt(Nk) (model_operations.py:85)")
     known = {k for k, _ in blob_schema(c)}
@@ -131,10 +126,10 @@ def stack_layers(state_dict_16, config_32, residual_scale=0.5):
         if key.startswith("sum."):
             parts = key.split(".")
             src = ".".join(["sum", str(int(parts[1]) // 2)] + parts[2:])
-            a = _to_numpy(state_dict_16[src]).astype(np.float32)
+            a = host(state_dict_16[src]).astype(np.float32)
             if key.endswith("su.qpm.4.weight") or key.endswith("su.qpm.4.bias") or key.endswith("su.ppm.0.weight"):
                 a = a * np.float32(residual_scale)
             out[key] = a
         else:
-            out[key] = _to_numpy(state_dict_16[key]).astype(np.float32)
+            out[key] = host(state_dict_16[key]).astype(np.float32)
     return unflatten_blob(c, flatten_state_dict(c, out))

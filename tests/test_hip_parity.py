@@ -295,6 +295,36 @@ def test_knn_ragged_batch_with_coincident_atoms_vs_host_contract():
     assert ids_dev.is_cuda and torch.equal(ids_dev.cpu(), torch.from_numpy(ids))
 
 
+def test_host_arrays_beside_a_rocm_lead_go_to_its_gpu():
+    """X decides where forward_segments / knn_tie_rows run (pesto_amd._lib.Side): with a ROCm X, ids_topk / q0 / res_of_atom given as numpy
+    arrays or CPU tensors are copied to its GPU, never passed on as host pointers - the bits of the all-device call, which are the bits of
+    the host call. The headline's ROCm inputs are used as they are."""
+    import torch
+    from pesto_amd import _lib
+    g = golden("fwd_i_v4_0_2CUA")
+    X, ids, q, roa = g["X"], g["ids_topk"].astype(np.int64), onehot(g["q_idx"], 30), g["res_of_atom"].astype(np.int32)
+    n, R = X.shape[0], int(g["res_of_atom"].max()) + 1
+    m = _model("i_v4_0").to("cuda:0")
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    Xd, idsd = d(X), d(ids)
+    side = _lib.Side(Xd, 0)
+    assert side.put(Xd, np.float32, (n, 3)) is Xd and side.put(idsd, (np.int64, np.int32)) is idsd      # no copy, no kernel
+    for sizes in (None, [n]):                                   # pesto_forward / pesto_forward_structures
+        z_host = m.forward_segments(X, ids, q, roa, R, sizes=sizes)
+        z_dev = m.forward_segments(Xd, idsd, d(q), d(roa), R, sizes=sizes)
+        assert np.array_equal(z_dev.cpu().numpy(), z_host)
+        for ids_, q_, roa_ in ((ids, q, roa), (torch.from_numpy(ids), torch.from_numpy(q), torch.from_numpy(roa)),
+                               (ids.astype(np.int32), q.astype(np.float64), roa.tolist())):
+            z_mix = m.forward_segments(Xd, ids_, q_, roa_, R, sizes=sizes)
+            assert z_mix.is_cuda and torch.equal(z_mix, z_dev)
+    ids_k = m.knn_collate(X, [n])
+    fl_host = m.knn_tie_rows(X, [n], ids_k)
+    fl_dev = m.knn_tie_rows(Xd, [n], d(ids_k))
+    assert fl_dev.is_cuda and np.array_equal(fl_dev.cpu().numpy(), fl_host)
+    for ids_ in (ids_k, torch.from_numpy(ids_k), ids_k.astype(np.int32)):
+        assert torch.equal(m.knn_tie_rows(Xd, [n], ids_), fl_dev)
+
+
 def test_knn_feeds_forward_end_to_end():
     """kNN on the GPU -> forward on the GPU gives the reference golden z (inputs: coordinates only, no host topology)."""
     g = golden("fwd_i_v4_0_2CUA")
@@ -362,6 +392,8 @@ def test_frames_device_tensors_strided_view():
     z2 = m.forward_frames(Xt.transpose(0, 1)[1:3], torch.from_numpy(g["ids_topk"]).cuda(), torch.from_numpy(onehot(g["q_idx"], 30)).cuda(),
                           torch.from_numpy(M).cuda(), frame_axis=0)   # a non-contiguous [F', N, 3] view
     assert torch.equal(z2, z[1:3])
+    z_host = m.forward_frames(g["X_traj"], g["ids_topk"].astype(np.int64), onehot(g["q_idx"], 30), M, frame_axis=1)   # from host memory
+    assert isinstance(z_host, np.ndarray) and np.array_equal(z.cpu().numpy(), z_host)
 
 
 def test_frames_bad_arguments():
@@ -403,6 +435,8 @@ def test_postprocess_matches_reference_sigmoid_and_encode_bfactor():
     assert np.abs(bf.cpu().numpy() - g["bfactor0"]).max() < 1e-5
     p_only, none = m.postprocess(z)
     assert none is None and torch.equal(p_only, p)
+    p_host, bf_host = m.postprocess(z.cpu().numpy(), M)                 # the same call from host memory: the same bits
+    assert np.array_equal(p.cpu().numpy(), p_host) and np.array_equal(bf.cpu().numpy(), bf_host)
 
 
 # ---------------------------------------------------------------------------------------------- apply_model.ipynb cell 6, natively

@@ -127,6 +127,9 @@ def test_bc_scores_match_reference(model, case, where):
         ps = [torch.from_numpy(p).cuda() for p in ps]
     got = bc_scores_batch(model, ys, ps)
     got = got.cpu().numpy() if hasattr(got, "cpu") else got
+    if where == "device":                                 # the same call from host memory (CPU tensors): the same bits
+        host = bc_scores_batch(model, [y.cpu() for y in ys], [p.cpu() for p in ps])
+        assert isinstance(host, torch.Tensor) and np.array_equal(got, host.numpy(), equal_nan=True)
     _check_scores(got, d["scores"], f"{case}/{where}")
     for i in (0, off.size - 2):                           # the single-structure form (its own weightless handle)
         one = bc_scoring(ys[i], ps[i])
