@@ -342,6 +342,40 @@ int pesto_interface_patches(pesto_model* m, int32_t n_struct, const int32_t* res
                             int32_t* patch_of, int32_t* n_patches, int32_t* patch_size, float* patch_mean, int32_t flags, int32_t ptr_kind,
                             void* stream);
 
+/* ---- dataset contacts (no GPU counterpart in the reference) ----
+ * Failures of the entry point below are reported through pesto_contacts_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the evaluation group it uses the handle for its device, after
+ * pesto_synchronize(m), and allocates its buffers stream-ordered per call; it keeps no state between calls. */
+const char* pesto_contacts_last_error(void);
+
+/* replaces: extract_all_contacts / locate_contacts (src/data_encoding.py:116-167, a dense torch distance matrix per pair of subunits) and
+ * contacts_types + pack_contacts_data (processing/build_dataset.py:41-83, a dense [R0,R1,79,79] bool map per pair) for n_struct assemblies.
+ * Assembly s owns atoms [struct_offsets[s], struct_offsets[s+1]) (HOST array). Per atom: X float32 [n_total,3]; subunit int32 in
+ * [0, n_sub), n_sub <= 65535, ascending along the atoms (each subunit one contiguous run, in the reference's subunit order; a new id at
+ * every assembly start); residue int32 in [0, 8192) (the column of encode_structure's M within the subunit); type int32 in [-1, n_types),
+ * n_types <= 128 (the index of the atom's resname in molecule_ids, -1 for none).
+ * Contacts: every (a, b) of one assembly with subunit[a] < subunit[b] and sqrt(fma(z,z, fma(y,y, x*x))) < r_thr (torch.norm's float32
+ * rounding), grouped by (subunit[a], subunit[b]) ascending and within a group by a, then b - the reference's torch.where order.
+ *   pairs_out int32 [cap_pairs,2] (batch atom indices a, b), d_out float32 [cap_pairs] (the distance)
+ *   groups_out int32 [cap_groups,4]: per group (subunit i, subunit j, its first row of pairs_out, its number of typed keys)
+ *   keys_out uint16 [cap_pairs,4]: per group in turn, torch.where of contacts_types' Y, sorted (r0, r1, t0, t1) rows. Y[r0, r1] is the
+ *             [n_types, n_types] slab of the LAST pair (a, b) of the group, in the order above, with residue[a] = r0 and residue[b] = r1
+ *             (the reference's index_put_ with repeated residue pairs): one row (r0, r1, type[a], type[b]) when both types are defined,
+ *             none otherwise
+ *   rkeys_out uint16 [cap_pairs,4]: the same rows for the swapped direction, (r1, r0, t1, t0) sorted (torch.where of Y.permute(1,0,3,2))
+ *   T_out uint8 [cap_groups,n_types,n_types]: T[g][t0][t1] = 1 where group g has such a key (contacts_types' T)
+ *   ties_out uint8 [n_total]: 1 where an atom of another subunit lies at EXACTLY r_thr (a differently rounded distance could decide it)
+ *   sizes_out int64 [3] (HOST): K pairs, G groups, U typed keys (both directions have U). The outputs are complete when K <= cap_pairs and
+ *             G <= cap_groups (cap_groups < 2^22); otherwise sizes_out holds what is known (K always; G and U -1 while K > cap_pairs) and the call must be
+ *             repeated with larger capacities (the count is the one synchronisation of a call).
+ * Cell grid (cells >= r_thr wide), count -> scan -> emit in (a, b) order, a stable radix regroup, stable radix sorts of packed 64-bit
+ * keys: every output is bit-identical from call to call and between a batch and its assemblies one at a time. The call synchronises
+ * `stream`; an id, residue or type outside its range makes it return PESTO_ERR_INVALID. */
+int pesto_contacts(pesto_model* m, int64_t n_total, int32_t n_struct, const int32_t* struct_offsets, int32_t n_sub, const float* X,
+                   const int32_t* subunit, const int32_t* residue, const int32_t* type, int32_t n_types, float r_thr, int64_t cap_pairs,
+                   int64_t cap_groups, int32_t* pairs_out, float* d_out, int32_t* groups_out, uint16_t* keys_out, uint16_t* rkeys_out,
+                   uint8_t* T_out, uint8_t* ties_out, int64_t* sizes_out, int32_t ptr_kind, void* stream);
+
 /* ---- test hooks ----
  * Debug twins of the shipped kernels, selected per handle (the parity tests run every stage through each of them):
  * layer_kernels 0 = shipped (hybrid first layer; arithmetic per the precision policy), 1 = reference-formulation fp32 VALU

@@ -11,7 +11,12 @@ the caller (apply.save_results) then has the .npz store, and says so - nothing i
 
 Files written here open with ``h5py.File(path)`` / ``h5dump``; files written by the reference's loop (h5py defaults: contiguous
 little-endian float32) read back with H5Store(path).  Not covered: filtered datasets (the reference's INPUT stores use h5py's own
-"lzf" filter, src/dataset.py:63 - a plugin the C library does not ship), attributes, compound types.
+"lzf" filter, src/dataset.py:63 - a plugin the C library does not ship), compound types.
+
+The dataset layout of the reference's build (processing/build_dataset.py, written with h5py) needs a little more, added below the store's
+result-file interface without changing it: groups, attributes on groups and datasets (H5Store.create_group / set_attrs / attrs), datasets
+written with create_dataset (optional deflate, h5py's compression="gzip") and read with read(): fixed-length NULLPAD ASCII strings (what
+h5py writes for np.string_ arrays) and numpy bool stored as h5py stores it, an 8-bit enum FALSE = 0 / TRUE = 1 that h5py reads back as bool.
 """
 import ctypes
 import ctypes.util
@@ -27,7 +32,9 @@ herr_t = ctypes.c_int
 H5F_ACC_RDONLY, H5F_ACC_TRUNC = 0, 2
 H5P_DEFAULT, H5S_ALL = 0, 0
 H5_INDEX_NAME, H5_ITER_NATIVE = 0, 2
-H5T_INTEGER, H5T_FLOAT = 0, 1
+H5T_INTEGER, H5T_FLOAT, H5T_STRING, H5T_ENUM = 0, 1, 3, 8
+H5T_STR_NULLPAD, H5T_CSET_ASCII = 1, 0
+H5_ITER_INC = 0
 H5T_ORDER_LE = 0
 H5T_SGN_NONE = 0
 
@@ -100,6 +107,30 @@ def load():
         "H5Tclose": (herr_t, [hid_t]),
         "H5Lexists": (ctypes.c_int, [hid_t, ctypes.c_char_p, hid_t]),
         "H5Ldelete": (herr_t, [hid_t, ctypes.c_char_p, hid_t]),
+        # groups, attributes, strings, enums, filters (the dataset layout)
+        "H5Gcreate2": (hid_t, [hid_t, ctypes.c_char_p, hid_t, hid_t, hid_t]),
+        "H5Gclose": (herr_t, [hid_t]),
+        "H5Oopen": (hid_t, [hid_t, ctypes.c_char_p, hid_t]),
+        "H5Oclose": (herr_t, [hid_t]),
+        "H5Acreate2": (hid_t, [hid_t, ctypes.c_char_p, hid_t, hid_t, hid_t, hid_t]),
+        "H5Aopen": (hid_t, [hid_t, ctypes.c_char_p, hid_t]),
+        "H5Awrite": (herr_t, [hid_t, hid_t, ctypes.c_void_p]),
+        "H5Aread": (herr_t, [hid_t, hid_t, ctypes.c_void_p]),
+        "H5Aget_space": (hid_t, [hid_t]),
+        "H5Aget_type": (hid_t, [hid_t]),
+        "H5Aclose": (herr_t, [hid_t]),
+        "H5Aiterate2": (herr_t, [hid_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(hsize_t), ctypes.c_void_p, ctypes.c_void_p]),
+        "H5Tcopy": (hid_t, [hid_t]),
+        "H5Tset_size": (herr_t, [hid_t, ctypes.c_size_t]),
+        "H5Tset_strpad": (herr_t, [hid_t, ctypes.c_int]),
+        "H5Tset_cset": (herr_t, [hid_t, ctypes.c_int]),
+        "H5Tenum_create": (hid_t, [hid_t]),
+        "H5Tenum_insert": (herr_t, [hid_t, ctypes.c_char_p, ctypes.c_void_p]),
+        "H5Tget_super": (hid_t, [hid_t]),
+        "H5Tget_nmembers": (ctypes.c_int, [hid_t]),
+        "H5Pset_chunk": (herr_t, [hid_t, ctypes.c_int, ctypes.POINTER(hsize_t)]),
+        "H5Pset_deflate": (herr_t, [hid_t, ctypes.c_uint]),
+        "H5Zfilter_avail": (ctypes.c_int, [ctypes.c_int]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -287,6 +318,119 @@ class H5Store:
             raise KeyError(key)
         return name.encode()
 
+    # ---- the dataset layout: groups, attributes, strings, bool, deflate
+    def create_group(self, path):
+        """Create the group ``path`` and any missing parents (h5py's File.create_group; an existing group is an error there too)."""
+        if self.mode != "w":
+            raise H5Error("store is read-only")
+        g = self._lib.H5Gcreate2(self._id, self._name(path), self._lcpl, H5P_DEFAULT, H5P_DEFAULT)
+        if g < 0:
+            raise H5Error(f"HDF5: cannot create group {path}")
+        self._lib.H5Gclose(g)
+
+    def create_dataset(self, name, data, compression=None, attrs=None):
+        """h5py's create_dataset(name, data=...) for numeric, bool (8-bit enum FALSE / TRUE) and fixed-length bytes ('S<n>': NULLPAD
+        ASCII strings) arrays. compression: None (contiguous) or "gzip" (deflate level 4 in one chunk; H5Unavailable when the library
+        has no deflate filter). attrs: {name: value} written on the dataset (set_attrs)."""
+        if self.mode != "w":
+            raise H5Error("store is read-only")
+        if compression not in (None, "gzip"):
+            raise ValueError(f"compression must be None or 'gzip', got {compression!r}")
+        a = np.ascontiguousarray(data)
+        lib = self._lib
+        tid, own = _file_type(a)
+        dims = (hsize_t * max(a.ndim, 1))(*a.shape)
+        space = _check(lib.H5Screate_simple(a.ndim, dims if a.ndim else None, None), "H5Screate_simple")
+        dcpl = H5P_DEFAULT
+        try:
+            if compression and a.ndim and a.size:
+                if lib.H5Zfilter_avail(1) <= 0:                           # H5Z_FILTER_DEFLATE
+                    raise H5Unavailable("this HDF5 C library has no deflate filter")
+                dcpl = _check(lib.H5Pcreate(_gid("H5P_CLS_DATASET_CREATE_ID_g")), "H5Pcreate(dataset creation)")
+                _check(lib.H5Pset_chunk(dcpl, a.ndim, dims), "H5Pset_chunk")
+                _check(lib.H5Pset_deflate(dcpl, 4), "H5Pset_deflate")
+            ds = _check(lib.H5Dcreate2(self._id, self._name(name), tid, space, self._lcpl, dcpl, H5P_DEFAULT), f"H5Dcreate2({name})")
+            try:
+                if a.size:
+                    _check(lib.H5Dwrite(ds, tid, H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data_as(ctypes.c_void_p)), f"H5Dwrite({name})")
+            finally:
+                lib.H5Dclose(ds)
+        finally:
+            if dcpl != H5P_DEFAULT:
+                lib.H5Pclose(dcpl)
+            lib.H5Sclose(space)
+            if own:
+                lib.H5Tclose(tid)
+        if attrs:
+            self.set_attrs(name, attrs)
+
+    def set_attrs(self, path, attrs):
+        """Write {name: value} as attributes of the group or dataset ``path`` (h5py's obj.attrs[name] = value): numbers and tuples of
+        ints as arrays (int64 for Python ints, as h5py stores a shape), numpy arrays as they are, bool arrays as the 8-bit enum."""
+        if self.mode != "w":
+            raise H5Error("store is read-only")
+        lib = self._lib
+        obj = _check(lib.H5Oopen(self._id, self._name(path), H5P_DEFAULT), f"H5Oopen({path})")
+        try:
+            for k, v in attrs.items():
+                a = np.ascontiguousarray(np.asarray(v, dtype=np.int64) if isinstance(v, (tuple, list, int)) and not isinstance(v, bool)
+                                         else np.asarray(v))
+                tid, own = _file_type(a)
+                dims = (hsize_t * max(a.ndim, 1))(*a.shape)
+                space = _check(lib.H5Screate_simple(a.ndim, dims if a.ndim else None, None), "H5Screate_simple")
+                try:
+                    at = _check(lib.H5Acreate2(obj, str(k).encode(), tid, space, H5P_DEFAULT, H5P_DEFAULT), f"H5Acreate2({path}:{k})")
+                    try:
+                        if a.size:
+                            _check(lib.H5Awrite(at, tid, a.ctypes.data_as(ctypes.c_void_p)), f"H5Awrite({path}:{k})")
+                    finally:
+                        lib.H5Aclose(at)
+                finally:
+                    lib.H5Sclose(space)
+                    if own:
+                        lib.H5Tclose(tid)
+        finally:
+            lib.H5Oclose(obj)
+
+    def attrs(self, path):
+        """{name: numpy value} of the attributes of the group or dataset ``path``, in name order (the 8-bit enum as bool)."""
+        lib = self._lib
+        obj = lib.H5Oopen(self._id, self._name(path), H5P_DEFAULT)
+        if obj < 0:
+            raise KeyError(path)
+        names = []
+        cb_t = ctypes.CFUNCTYPE(herr_t, hid_t, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p)
+
+        def visit(_loc, name, _info, _data):
+            names.append(name.decode())
+            return 0
+
+        try:
+            cb = cb_t(visit)
+            _check(lib.H5Aiterate2(obj, H5_INDEX_NAME, H5_ITER_INC, None, ctypes.cast(cb, ctypes.c_void_p), None), "H5Aiterate2")
+            out = {}
+            for n in names:
+                at = _check(lib.H5Aopen(obj, n.encode(), H5P_DEFAULT), f"H5Aopen({n})")
+                try:
+                    out[n] = _read_object(lib, at, lib.H5Aget_space, lib.H5Aget_type, lambda mt, buf: lib.H5Aread(at, mt, buf), n)
+                finally:
+                    lib.H5Aclose(at)
+            return out
+        finally:
+            lib.H5Oclose(obj)
+
+    def read(self, key):
+        """The dataset ``key`` as numpy: what __getitem__ reads, plus fixed-length strings (bytes, 'S<n>') and the 8-bit bool enum (bool)."""
+        lib = self._lib
+        ds = lib.H5Dopen2(self._id, self._name(key), H5P_DEFAULT)
+        if ds < 0:
+            raise KeyError(key)
+        try:
+            return _read_object(lib, ds, lib.H5Dget_space, lib.H5Dget_type,
+                                lambda mt, buf: lib.H5Dread(ds, mt, H5S_ALL, H5S_ALL, H5P_DEFAULT, buf), key)
+        finally:
+            lib.H5Dclose(ds)
+
     # ---- life cycle
     def flush(self):
         if self._id >= 0:
@@ -313,3 +457,66 @@ class H5Store:
             self.close()
         except Exception:
             pass
+
+
+def _bool_type():
+    """h5py's bool: an enum over a signed 8-bit integer, FALSE = 0, TRUE = 1 (a new type id; the caller closes it)."""
+    lib = load()
+    t = _check(lib.H5Tenum_create(_gid("H5T_NATIVE_INT8_g")), "H5Tenum_create")
+    for name, v in ((b"FALSE", 0), (b"TRUE", 1)):
+        c = ctypes.c_int8(v)
+        _check(lib.H5Tenum_insert(t, name, ctypes.byref(c)), "H5Tenum_insert")
+    return t
+
+
+def _file_type(a):
+    """(type id, owned) for the elements of numpy array ``a``: the native numeric types, the bool enum, fixed-length NULLPAD ASCII."""
+    lib = load()
+    if a.dtype == np.bool_:
+        return _bool_type(), True
+    if a.dtype.kind == "S":
+        t = _check(lib.H5Tcopy(_gid("H5T_C_S1_g")), "H5Tcopy")
+        _check(lib.H5Tset_size(t, max(1, a.dtype.itemsize)), "H5Tset_size")
+        _check(lib.H5Tset_strpad(t, H5T_STR_NULLPAD), "H5Tset_strpad")
+        _check(lib.H5Tset_cset(t, H5T_CSET_ASCII), "H5Tset_cset")
+        return t, True
+    if a.dtype not in _NATIVE:
+        raise TypeError(f"dtype {a.dtype} has no HDF5 mapping here (numbers, bool and fixed-length bytes do)")
+    return _gid(_NATIVE[a.dtype]), False
+
+
+def _read_object(lib, obj, get_space, get_type, read, what):
+    """Read a dataset or attribute: numbers (native), fixed-length strings (bytes) and 8-bit enums of FALSE / TRUE (bool)."""
+    space = _check(get_space(obj), "get_space")
+    try:
+        nd = _check(lib.H5Sget_simple_extent_ndims(space), "H5Sget_simple_extent_ndims")
+        dims = (hsize_t * max(nd, 1))()
+        if nd:
+            _check(lib.H5Sget_simple_extent_dims(space, dims, None), "H5Sget_simple_extent_dims")
+        shape = tuple(int(dims[i]) for i in range(nd))
+    finally:
+        lib.H5Sclose(space)
+    ft = _check(get_type(obj), "get_type")
+    mt, own, post = None, False, None
+    try:
+        cls, size = lib.H5Tget_class(ft), int(lib.H5Tget_size(ft))
+        if cls == H5T_FLOAT and size in (4, 8):
+            dt = np.dtype(np.float32 if size == 4 else np.float64)
+        elif cls == H5T_INTEGER and size in (1, 2, 4, 8):
+            dt = np.dtype(("u" if lib.H5Tget_sign(ft) == H5T_SGN_NONE else "i") + str(size))
+        elif cls == H5T_STRING:
+            dt = np.dtype(f"S{size}")
+            mt = _check(lib.H5Tcopy(ft), "H5Tcopy")           # the file's own string type: the library copies the bytes as they are
+            own = True
+        elif cls == H5T_ENUM and size == 1:
+            dt, mt, own, post = np.dtype(np.int8), _bool_type(), True, (lambda v: v.astype(bool))
+        else:
+            raise H5Error(f"HDF5: {what}: type class {cls} of {size} bytes is not read here")
+        out = np.empty(shape, dt)
+        if out.size:
+            _check(read(mt if mt is not None else _gid(_NATIVE[dt]), out.ctypes.data_as(ctypes.c_void_p)), f"read({what})")
+        return post(out) if post else out
+    finally:
+        if own:
+            lib.H5Tclose(mt)
+        lib.H5Tclose(ft)
