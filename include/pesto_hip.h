@@ -376,6 +376,76 @@ int pesto_contacts(pesto_model* m, int64_t n_total, int32_t n_struct, const int3
                    int64_t cap_groups, int32_t* pairs_out, float* d_out, int32_t* groups_out, uint16_t* keys_out, uint16_t* rkeys_out,
                    uint8_t* T_out, uint8_t* ties_out, int64_t* sizes_out, int32_t ptr_kind, void* stream);
 
+/* ---- MD ensemble analysis (the reference's md_analysis/mdtraj_utils; its statistical contacts model is a per-frame torch loop) ----
+ * Failures of the entry points below are reported through pesto_trajectory_last_error() (thread-local message of the last failing call
+ * of this group; an invalid handle's message is copied there too). Like the evaluation group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ * Trajectories are float32 [F,N,3] (mdtraj's xyz). Distances are the float32 ones of NumPy and torch,
+ *     d = sqrt((dx*dx + dy*dy) + dz*dz), every operation rounded, the root correctly rounded,
+ * and every output is bit-identical from call to call (integer counts; floating-point sums in double in a fixed order). */
+const char* pesto_trajectory_last_error(void);
+
+enum {
+    PESTO_TRAJECTORY_MAX_FRAMES = 1 << 24,    /* the reference counts frames in float32 */
+    PESTO_TRAJECTORY_MAX_BINS = 128,          /* one LDS counter per (bin, thread) */
+    PESTO_TRAJECTORY_MAX_MAP_ATOMS = 12288    /* Na + Nb of pesto_residue_contact_maps: one frame's atoms in LDS */
+};
+
+/* replaces: contacts_distribution (md_analysis/mdtraj_utils/statistical_contacts_model.py:7-30) for xyz_a [F,Na,3] against xyz_b [F,Nb,3]
+ * (the same pointer for a trajectory against itself). edges: n_bins + 1 strictly increasing finite float64 values within the float32
+ * range (HOST array), 1 <= n_bins <= PESTO_TRAJECTORY_MAX_BINS; F <= PESTO_TRAJECTORY_MAX_FRAMES; Na * Nb * n_bins < 2^31.
+ *     counts_out uint32 [Na,Nb,n_bins]: the number of frames with edges[b] <= d < edges[b+1] (float32 d against the float64 edge;
+ *                a NaN distance is in no bin)
+ *     P_out float32 [Na,Nb,n_bins] or NULL: float32(count) / (float32(sum over b of count) + 1e-6f), the reference's normalisation
+ * frame_splits: 0, or the number of frame ranges counted by separate workgroups and added as integers (test hook; the result does not
+ * depend on it). */
+int pesto_contact_counts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, const float* xyz_a, const float* xyz_b, int32_t n_bins,
+                         const double* edges, uint32_t* counts_out, float* P_out, int32_t frame_splits, int32_t ptr_kind, void* stream);
+
+/* replaces: StatisticalContactsModel.loglikelihood (statistical_contacts_model.py:47-75). Arguments as pesto_contact_counts; P float32
+ * [Na,Nb,n_bins] is the fitted model. L_out float32 [F]: -mean over (i, j, b) of log(1 - PQ + floor(PQ)), PQ = P[i,j,b] where frame f puts
+ * pair (i, j) into bin b and 0 elsewhere, evaluated in double from the float32 P. Device scratch: one double per 32 x 32 tile of pairs and
+ * frame, at most 64 MB (or one 64-frame chunk of every tile, if larger): the frames go through in passes. */
+int pesto_contact_loglik(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, const float* xyz_a, const float* xyz_b, int32_t n_bins,
+                         const double* edges, const float* P, float* L_out, int32_t ptr_kind, void* stream);
+
+/* replaces: div_KL (statistical_contacts_model.py:78-81). P, Q float32 [n_pairs,n_bins], n_pairs * n_bins < 2^31; D_out float32 [n_pairs]:
+ * -sum over b of P log(R), R = Q / (P + 1e-6f), R = 1 where R < 1e-6f, evaluated in double from the float32 inputs. */
+int pesto_contact_div_kl(pesto_model* m, int64_t n_pairs, int32_t n_bins, const float* P, const float* Q, float* D_out, int32_t ptr_kind,
+                         void* stream);
+
+/* replaces: the residue-pair loop of fnat (md_analysis/mdtraj_utils/trajectory_utils.py:369-379). xyz_a [F,Na,3], xyz_b [F,Nb,3],
+ * Na + Nb <= PESTO_TRAJECTORY_MAX_MAP_ATOMS. perm_a int32 [Na]: the atoms of A ordered by residue row; off_a int32 [Ra + 1]: residue r owns
+ * perm_a[off_a[r] .. off_a[r+1]), every residue at least one atom (likewise perm_b, off_b). maps_out uint8 [F,Ra,Rb]: 1 where an atom
+ * pair of the two residues has float32(d * scale) < r_thr (NumPy's float32 evaluation of pairwise_distance_matrix(...) < r_thr). */
+int pesto_residue_contact_maps(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, const float* xyz_a, const float* xyz_b, int32_t Ra, int32_t Rb,
+                               const int32_t* perm_a, const int32_t* off_a, const int32_t* perm_b, const int32_t* off_b, float r_thr, float scale,
+                               uint8_t* maps_out, int32_t ptr_kind, void* stream);
+
+/* replaces: the numerator and denominator of fnat (trajectory_utils.py:386). maps uint8 [F,n], maps_ref uint8 [F_ref,n], F_ref = 1 or F.
+ * native_out int64 [F]: the number of k with maps[f,k] and maps_ref[f or 0,k] set; ref_total_out int64 [1]: the number of set entries
+ * of maps_ref. */
+int pesto_native_contacts(pesto_model* m, int64_t F, int64_t F_ref, int64_t n, const uint8_t* maps_ref, const uint8_t* maps, int64_t* native_out,
+                          int64_t* ref_total_out, int32_t ptr_kind, void* stream);
+
+/* replaces: superpose_transform, the transform in superpose and the expression of rmsd (trajectory_utils.py:190-230, 308-325) for every
+ * frame of xyz [F,N,3] onto xyz_ref [F_ref,N_ref,3], F_ref = 1 or F, fitted on n_sel >= 3 atoms: sel_ref / sel int32 [n_sel] atom
+ * indices, or NULL for all atoms of that side (then n_sel equals its atom count). Per frame, in double: t, t_ref = means of the
+ * selected atoms; U S V^T = svd((ref - t_ref)^T (xyz - t)) by one-sided Jacobi; R = V diag(1, 1, det(U) det(V)) U^T. A selection that
+ * leaves R undetermined (collinear or coincident atoms) gets some proper rotation of the same fit, never NaN.
+ *     t_out float32 [F,3], R_out float32 [F,3,3], t_ref_out float32 [F_ref,3]:  (xyz - t) R + t_ref lies on xyz_ref
+ *     xyz_out float32 [F,N,3] or NULL: every atom transformed (from the double t, R, t_ref)
+ *     rmsd_out float32 [F]: sqrt(mean over the selected atoms of the squared deviation from the reference's) * scale */
+int pesto_superpose(pesto_model* m, int64_t F, int64_t F_ref, int64_t N_ref, int64_t N, int64_t n_sel, const float* xyz_ref, const float* xyz,
+                    const int32_t* sel_ref, const int32_t* sel, double scale, float* t_out, float* R_out, float* t_ref_out, float* xyz_out,
+                    float* rmsd_out, int32_t ptr_kind, void* stream);
+
+/* replaces: Xp = X M / count at the end of md_analysis/apply_model_md.ipynb. X_frames [F,N,3]; perm int32 [N]: the atoms ordered by
+ * residue row (ascending within a row); off int32 [R + 1]. out float32 [F,R,3]: the mean of each residue's atoms, summed in double in
+ * atom order (NaN for a residue without atoms). */
+int pesto_residue_centroids(pesto_model* m, int64_t F, int64_t N, int64_t R, const float* X_frames, const int32_t* perm, const int32_t* off,
+                            float* out, int32_t ptr_kind, void* stream);
+
 /* ---- test hooks ----
  * Debug twins of the shipped kernels, selected per handle (the parity tests run every stage through each of them):
  * layer_kernels 0 = shipped (hybrid first layer; arithmetic per the precision policy), 1 = reference-formulation fp32 VALU

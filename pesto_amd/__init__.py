@@ -6,7 +6,9 @@ here: a Python host mirror of the reference Module API over a C-ABI HIP library.
 from .config import CONFIGS, config_i_v3_0, config_i_v3_1, config_i_v4_0, config_i_v4_1, config_model  # noqa: F401
 
 __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_assemblies", "patches", "interface_patches",
-           "interface_patches_batch", "residue_ca", "save_patches", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
+           "interface_patches_batch", "residue_ca", "save_patches", "trajectory", "StatisticalContactsModel", "contacts_distribution", "contact_counts",
+           "div_KL", "interface_ensemble_comparison", "residue_contact_maps", "native_contacts", "fnat", "superpose_transform", "superpose", "rmsd",
+           "residue_centroids", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch or the built library
@@ -21,4 +23,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         pa = importlib.import_module(".patches", __name__)
         return pa if name == "patches" else getattr(pa, name)
+    if name in ("trajectory", "StatisticalContactsModel", "contacts_distribution", "contact_counts", "div_KL", "interface_ensemble_comparison",
+                "residue_contact_maps", "native_contacts", "fnat", "superpose_transform", "superpose", "rmsd", "residue_centroids"):
+        import importlib
+        tr = importlib.import_module(".trajectory", __name__)
+        return tr if name == "trajectory" else getattr(tr, name)
     raise AttributeError(name)

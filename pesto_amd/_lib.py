@@ -67,6 +67,8 @@ ABI_SYMBOLS = [
     "pesto_set_async_auto", "pesto_debug_host_only", "pesto_knn_tie_rows", "pesto_set_auto_state_limit", "pesto_set_auto_pad_trigger",
     "pesto_get_auto_counters", "pesto_interface_labels", "pesto_bc_scores", "pesto_eval_last_error",
     "pesto_interface_patches", "pesto_patches_last_error", "pesto_contacts", "pesto_contacts_last_error",
+    "pesto_trajectory_last_error", "pesto_contact_counts", "pesto_contact_loglik", "pesto_contact_div_kl", "pesto_residue_contact_maps",
+    "pesto_native_contacts", "pesto_superpose", "pesto_residue_centroids",
 ]
 
 _lib = None
@@ -137,12 +139,23 @@ def load():
     lib.pesto_contacts_last_error.argtypes = []
     lib.pesto_contacts.argtypes = [c_p, i64, i32, c_p, i32, c_p, c_p, c_p, c_p, i32, ctypes.c_float, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p,
                                    c_p, c_p, i32, c_p]
+    lib.pesto_trajectory_last_error.restype = ctypes.c_char_p
+    lib.pesto_trajectory_last_error.argtypes = []
+    lib.pesto_contact_counts.argtypes = [c_p, i64, i64, i64, c_p, c_p, i32, c_p, c_p, c_p, i32, i32, c_p]
+    lib.pesto_contact_loglik.argtypes = [c_p, i64, i64, i64, c_p, c_p, i32, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_contact_div_kl.argtypes = [c_p, i64, i32, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_residue_contact_maps.argtypes = [c_p, i64, i64, i64, c_p, c_p, i32, i32, c_p, c_p, c_p, c_p, ctypes.c_float, ctypes.c_float,
+                                               c_p, i32, c_p]
+    lib.pesto_native_contacts.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_superpose.argtypes = [c_p, i64, i64, i64, i64, i64, c_p, c_p, c_p, c_p, ctypes.c_double, c_p, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_residue_centroids.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_stage_embed.argtypes = [c_p, i64, c_p, c_p]
     lib.pesto_stage_unpack.argtypes = [c_p, i64, i32, c_p, c_p, i32, c_p, c_p]
     lib.pesto_stage_layer.argtypes = [c_p, i32, c_p, c_p]
     lib.pesto_stage_pool.argtypes = [c_p, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p]
     for name in ABI_SYMBOLS:
-        if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error"):
+        if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error",
+                        "pesto_trajectory_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
