@@ -446,6 +446,40 @@ int pesto_superpose(pesto_model* m, int64_t F, int64_t F_ref, int64_t N_ref, int
 int pesto_residue_centroids(pesto_model* m, int64_t F, int64_t N, int64_t R, const float* X_frames, const int32_t* perm, const int32_t* off,
                             float* out, int32_t ptr_kind, void* stream);
 
+/* ---- solvent-accessible surface area (the reference's two uses of md.shrake_rupley) ----
+ * replaces: wrapper_solvent_accessible_surface_area (interfaceome/solvent_accessible_surface_area.py:27-31, one structure at a time in a
+ * two-process pool) and sasa (md_analysis/mdtraj_utils/trajectory_utils.py:428-438, a Python loop over the frames).
+ * Failures are reported through pesto_sasa_last_error() (thread-local; an invalid handle's message is copied there too). Like the
+ * trajectory group the entry point uses the handle for its device, allocates its buffers stream-ordered per call, keeps no state between
+ * calls and synchronises `stream`; pointers are host or device memory according to ptr_kind, struct_offsets is always HOST memory.
+ *
+ * Definition. X float32 [F,n_total,3]; radius float32 [n_total], the atomic plus the probe radius; points float32 [P,3], the sphere
+ * points (finite; unit vectors for a meaningful area); the atoms struct_offsets[s] .. struct_offsets[s+1] form structure s and only meet
+ * each other. Every operation below is rounded to float32 on its own, as written, without fused multiply-adds:
+ *     t[c]          = X[f,i,c] + (radius[i] * points[k,c])              c = x, y, z
+ *     d[c]          = t[c] - X[f,j,c]
+ *     q(f,i,k,j)    = (d.x*d.x + d.y*d.y) + d.z*d.z
+ *     buried(f,i,k) = some j != i of i's structure with finite X[f,j] and radius[j] has  q < radius[j]*radius[j]
+ *     count[f,i]    = number of k in [0, P) that are not buried
+ *     area[f,i]     = float32(((c0 * count) * radius[i]) * radius[i])    evaluated in double; the caller passes c0 = 4 pi / P
+ *     group[f,g]    = float32(sum of the double areas of the atoms perm[group_off[g] .. group_off[g+1]), in that order)
+ * This is mdtraj's Shrake-Rupley algorithm made exact: count is an integer that depends neither on the order in which occluders are
+ * visited, nor on the other structures of the launch, nor on the pruning (a cell grid per frame and structure and a distance test, both
+ * widened by a margin that covers the float32 rounding of t and q - the argument is at the top of pesto_sasa.hip). A comparison with a
+ * NaN is false: an atom with a non-finite coordinate or radius buries nothing and has count = P. Coincident atoms are no error (mdtraj
+ * exits on them). mdtraj evaluates the area in float32; this one may differ from it by a couple of units in the last place.
+ * Limits: 1 <= P <= PESTO_SASA_MAX_POINTS; 1 <= F * n_total < 2^31; n_struct >= 1 with strictly increasing offsets from 0 to n_total;
+ * group sums need 1 <= n_groups, F * n_groups < 2^31. They are checked before any launch (PESTO_ERR_INVALID).
+ *     counts_out int32 [F,n_total] or NULL, area_out float32 [F,n_total] or NULL, group_out float32 [F,n_groups] or NULL (then perm,
+ *     group_off and n_groups are not read); at least one of the three. Every output is bit-identical from call to call. */
+const char* pesto_sasa_last_error(void);
+
+enum { PESTO_SASA_MAX_POINTS = 8192 };
+
+int pesto_sasa(pesto_model* m, int64_t F, int64_t n_total, int32_t n_struct, const int32_t* struct_offsets, const float* X, const float* radius,
+               int32_t P, const float* points, double c0, int32_t* counts_out, float* area_out, int32_t n_groups, const int32_t* perm,
+               const int32_t* group_off, float* group_out, int32_t ptr_kind, void* stream);
+
 /* ---- test hooks ----
  * Debug twins of the shipped kernels, selected per handle (the parity tests run every stage through each of them):
  * layer_kernels 0 = shipped (hybrid first layer; arithmetic per the precision policy), 1 = reference-formulation fp32 VALU

@@ -68,7 +68,7 @@ ABI_SYMBOLS = [
     "pesto_get_auto_counters", "pesto_interface_labels", "pesto_bc_scores", "pesto_eval_last_error",
     "pesto_interface_patches", "pesto_patches_last_error", "pesto_contacts", "pesto_contacts_last_error",
     "pesto_trajectory_last_error", "pesto_contact_counts", "pesto_contact_loglik", "pesto_contact_div_kl", "pesto_residue_contact_maps",
-    "pesto_native_contacts", "pesto_superpose", "pesto_residue_centroids",
+    "pesto_native_contacts", "pesto_superpose", "pesto_residue_centroids", "pesto_sasa_last_error", "pesto_sasa",
 ]
 
 _lib = None
@@ -149,13 +149,16 @@ def load():
     lib.pesto_native_contacts.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_superpose.argtypes = [c_p, i64, i64, i64, i64, i64, c_p, c_p, c_p, c_p, ctypes.c_double, c_p, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_residue_centroids.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_sasa_last_error.restype = ctypes.c_char_p
+    lib.pesto_sasa_last_error.argtypes = []
+    lib.pesto_sasa.argtypes = [c_p, i64, i64, i32, c_p, c_p, c_p, i32, c_p, ctypes.c_double, c_p, c_p, i32, c_p, c_p, c_p, i32, c_p]
     lib.pesto_stage_embed.argtypes = [c_p, i64, c_p, c_p]
     lib.pesto_stage_unpack.argtypes = [c_p, i64, i32, c_p, c_p, i32, c_p, c_p]
     lib.pesto_stage_layer.argtypes = [c_p, i32, c_p, c_p]
     lib.pesto_stage_pool.argtypes = [c_p, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p]
     for name in ABI_SYMBOLS:
         if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error",
-                        "pesto_trajectory_last_error"):
+                        "pesto_trajectory_last_error", "pesto_sasa_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
