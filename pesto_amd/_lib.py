@@ -165,8 +165,9 @@ def load():
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message (default pesto_last_error; the
-    evaluation and patch entry points keep their own, pesto_eval_last_error / pesto_patches_last_error)."""
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are six channels:
+    pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
+    pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error and pesto_sasa_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")

@@ -1,18 +1,12 @@
 // pesto_patches.hip - interface patches: the connected components of the distance-threshold graph over the residues predicted to be an
 // interface of one class, or of two classes at once, for every (structure, class pair) of a batch in one call.
 //
-// The C entry point (include/pesto_hip.h) lives here too. Like the evaluation group it needs only the handle's device (pesto_synchronize
-// sets it) and allocates its buffers stream-ordered per call, so it shares nothing with the forward's workspace.
-#include <hip/hip_runtime.h>
-
+// The C entry point (include/pesto_hip.h) lives here too, on the call plumbing of pesto_call.h.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 #include <vector>
 
-#include "../../include/pesto_hip.h"
+#include "pesto_call.h"
 
 namespace pesto {
 
@@ -274,26 +268,6 @@ __global__ __launch_bounds__(LARGE_THREADS) void k_patches_large_finish(PatchArg
     patch_finish<LARGE_THREADS>(A, it.s, it.k, n_nodes[blockIdx.x], gpar + it.base, gres + it.base, gx + it.base, gy + it.base, gz + it.base, wsum);
 }
 
-thread_local std::string g_patch_err;
-
-int pfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_patch_err = buf;
-    return code;
-}
-
-#define PT_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) { rc = pfail(PESTO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
-    } while (0)
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // smallest float s with sqrtf(s) >= d (d > 0 finite): sqrt(s) < d  <=>  s < s_star, for every float s (NaN compares false on both sides)
 float sqrt_threshold(float d) {
     float s = d * d;
@@ -310,7 +284,7 @@ float sqrt_threshold(float d) {
 
 using namespace pesto;
 
-const char* pesto_patches_last_error(void) { return g_patch_err.c_str(); }
+const char* pesto_patches_last_error(void) { return last_error(); }
 
 int pesto_interface_patches(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const float* xyz, const float* p,
                             const float* afs, const uint8_t* has_ca, int32_t n_sel, const int32_t* sel, float afs_thr, float p_thr, float d_thr,
@@ -318,26 +292,20 @@ int pesto_interface_patches(pesto_model* m, int32_t n_struct, const int32_t* res
                             void* stream) {
     if (n_struct < 1 || n_class < 1 || n_class > PESTO_PATCHES_MAX_CLASSES || n_sel < 1 || n_sel > PESTO_PATCHES_MAX_SEL || !res_offsets || !xyz ||
         !p || !sel || !patch_of || !n_patches || !patch_size || !patch_mean)
-        return pfail(PESTO_ERR_INVALID, "bad arguments");
-    if (flags & ~PESTO_PATCHES_FORCE_LARGE) return pfail(PESTO_ERR_INVALID, "unknown flags %d", flags);
-    if (ptr_kind != PESTO_PTR_HOST && ptr_kind != PESTO_PTR_DEVICE) return pfail(PESTO_ERR_INVALID, "ptr_kind must be PESTO_PTR_HOST or PESTO_PTR_DEVICE");
-    if (!(d_thr > 0.f) || !std::isfinite(d_thr)) return pfail(PESTO_ERR_INVALID, "d_thr must be a positive finite distance");
+        return fail(PESTO_ERR_INVALID, "bad arguments");
+    if (flags & ~PESTO_PATCHES_FORCE_LARGE) return fail(PESTO_ERR_INVALID, "unknown flags %d", flags);
+    if (int rc = check_ptr_kind(ptr_kind)) return rc;
+    if (!(d_thr > 0.f) || !std::isfinite(d_thr)) return fail(PESTO_ERR_INVALID, "d_thr must be a positive finite distance");
     for (int k = 0; k < n_sel; ++k)
         if (sel[2 * k] < 0 || sel[2 * k] > sel[2 * k + 1] || sel[2 * k + 1] >= n_class)
-            return pfail(PESTO_ERR_INVALID, "sel[%d] = (%d, %d): need 0 <= i <= j < n_class = %d", k, sel[2 * k], sel[2 * k + 1], n_class);
-    if (res_offsets[0] != 0) return pfail(PESTO_ERR_INVALID, "res_offsets must start at 0");
-    for (int s = 0; s < n_struct; ++s)
-        if (res_offsets[s + 1] <= res_offsets[s]) return pfail(PESTO_ERR_INVALID, "res_offsets: empty or unordered structure %d", s);
+            return fail(PESTO_ERR_INVALID, "sel[%d] = (%d, %d): need 0 <= i <= j < n_class = %d", k, sel[2 * k], sel[2 * k + 1], n_class);
+    if (res_offsets[0] != 0) return fail(PESTO_ERR_INVALID, "res_offsets must start at 0");
     const int64_t R = res_offsets[n_struct];
+    if (int rc = check_offsets(res_offsets, n_struct, R, "res_offsets")) return rc;
     if (R > PESTO_PATCHES_MAX_ROWS || R * n_class > 0x7fffffff || R * n_sel > 0x7fffffff)
-        return pfail(PESTO_ERR_INVALID, "too many rows: R = %lld (at most %d, and R * n_class, R * n_sel < 2^31)", (long long)R, PESTO_PATCHES_MAX_ROWS);
-    if (int rc = pesto_synchronize(m)) {
-        const char* e = pesto_last_error();
-        return pfail(rc, "%s", e ? e : "invalid model handle");
-    }
-    const bool dev = ptr_kind == PESTO_PTR_DEVICE;
+        return fail(PESTO_ERR_INVALID, "too many rows: R = %lld (at most %d, and R * n_class, R * n_sel < 2^31)", (long long)R, PESTO_PATCHES_MAX_ROWS);
+    if (int rc = begin(m, ptr_kind)) return rc;
     const bool force_large = (flags & PESTO_PATCHES_FORCE_LARGE) != 0;
-    hipStream_t stm = (hipStream_t)stream;
     // structures split by size; large items carry their scratch base and their share of the pair-tile grid
     std::vector<int> small;
     int cap = 0;
@@ -356,7 +324,7 @@ int pesto_interface_patches(pesto_model* m, int32_t n_struct, const int32_t* res
             items.push_back(LargeItem{s, k, (int)rows_large, nt});
             rows_large += Rs;
             const int64_t nb = (int64_t)blk_off.back() + (int64_t)nt * (nt + 1) / 2;
-            if (nb > 0x7fffffff) return pfail(PESTO_ERR_INVALID, "too many pair tiles for the large-structure path");
+            if (nb > 0x7fffffff) return fail(PESTO_ERR_INVALID, "too many pair tiles for the large-structure path");
             blk_off.push_back((int)nb);
         }
     }
@@ -364,72 +332,44 @@ int pesto_interface_patches(pesto_model* m, int32_t n_struct, const int32_t* res
     std::stable_sort(small.begin(), small.end(), [&](int a, int b) {
         return res_offsets[a + 1] - res_offsets[a] > res_offsets[b + 1] - res_offsets[b];
     });
-    if ((int64_t)small.size() * n_sel > 0x7fffffff) return pfail(PESTO_ERR_INVALID, "too many (structure, selection) items");
+    if ((int64_t)small.size() * n_sel > 0x7fffffff) return fail(PESTO_ERR_INVALID, "too many (structure, selection) items");
     const size_t rows = (size_t)R, n_out = rows * n_sel, n_items = items.size();
-    size_t o = 0;
-    auto take = [&o](size_t b) { const size_t at = o; o += align256(b); return at; };
-    const size_t oOff = take(((size_t)n_struct + 1) * 4), oSel = take((size_t)n_sel * 8), oSmall = take(std::max<size_t>(small.size(), 1) * 4),
-                 oItems = take(std::max<size_t>(n_items, 1) * sizeof(LargeItem)), oBlk = take((n_items + 1) * 4), oN = take(std::max<size_t>(n_items, 1) * 4),
-                 oG = take(std::max<size_t>((size_t)rows_large, 1) * 4 * 5);
-    const size_t oX = dev ? 0 : take(rows * 12), oP = dev ? 0 : take(rows * n_class * 4), oA = dev || !afs ? 0 : take(rows * 4),
-                 oC = dev || !has_ca ? 0 : take(rows), oPo = dev ? 0 : take(n_out * 4), oNp = dev ? 0 : take((size_t)n_struct * n_sel * 4),
-                 oPs = dev ? 0 : take(n_out * 4), oPm = dev ? 0 : take(n_out * 8);
-    char* w = nullptr;
-    int rc = 0;
+    Buffers bf(ptr_kind, stream);
+    const int iOff = bf.table(res_offsets, ((size_t)n_struct + 1) * 4), iSel = bf.table(sel, (size_t)n_sel * 8), iSmall = bf.table(small.data(), small.size() * 4),
+              iItems = bf.table(items.data(), n_items * sizeof(LargeItem)), iBlk = bf.table(blk_off.data(), (n_items + 1) * 4);
+    const int iX = bf.input(xyz, rows * 12), iP = bf.input(p, rows * n_class * 4), iA = bf.input(afs, rows * 4), iC = bf.input(has_ca, rows);
+    const int iPo = bf.output(patch_of, n_out * 4), iNp = bf.output(n_patches, (size_t)n_struct * n_sel * 4), iPs = bf.output(patch_size, n_out * 4),
+              iPm = bf.output(patch_mean, n_out * 8);
+    const int iN = bf.scratch(n_items * 4), iG = bf.scratch((size_t)rows_large * 4 * 5);
+    int rc = bf.upload();
     PatchArgs A;
-    const size_t smem = (size_t)cap * 5 * 4;
-    if (hipMallocAsync((void**)&w, o, stm) != hipSuccess) return pfail(PESTO_ERR_NOMEM, "device allocation of %zu bytes failed", o);
-    PT_TRY(hipMemcpyAsync(w + oOff, res_offsets, ((size_t)n_struct + 1) * 4, hipMemcpyHostToDevice, stm));
-    PT_TRY(hipMemcpyAsync(w + oSel, sel, (size_t)n_sel * 8, hipMemcpyHostToDevice, stm));
-    if (!small.empty()) PT_TRY(hipMemcpyAsync(w + oSmall, small.data(), small.size() * 4, hipMemcpyHostToDevice, stm));
-    if (n_items) {
-        PT_TRY(hipMemcpyAsync(w + oItems, items.data(), n_items * sizeof(LargeItem), hipMemcpyHostToDevice, stm));
-        PT_TRY(hipMemcpyAsync(w + oBlk, blk_off.data(), (n_items + 1) * 4, hipMemcpyHostToDevice, stm));
-    }
-    if (!dev) {
-        PT_TRY(hipMemcpyAsync(w + oX, xyz, rows * 12, hipMemcpyHostToDevice, stm));
-        PT_TRY(hipMemcpyAsync(w + oP, p, rows * n_class * 4, hipMemcpyHostToDevice, stm));
-        if (afs) PT_TRY(hipMemcpyAsync(w + oA, afs, rows * 4, hipMemcpyHostToDevice, stm));
-        if (has_ca) PT_TRY(hipMemcpyAsync(w + oC, has_ca, rows, hipMemcpyHostToDevice, stm));
-    }
     A.R = (int)R; A.n_class = n_class; A.n_sel = n_sel;
-    A.offsets = (const int*)(w + oOff);
-    A.sel = (const int*)(w + oSel);
-    A.xyz = dev ? xyz : (const float*)(w + oX);
-    A.p = dev ? p : (const float*)(w + oP);
-    A.afs = !afs ? nullptr : dev ? afs : (const float*)(w + oA);
-    A.has_ca = !has_ca ? nullptr : dev ? has_ca : (const unsigned char*)(w + oC);
+    A.offsets = bf.ptr<const int>(iOff);
+    A.sel = bf.ptr<const int>(iSel);
+    A.xyz = bf.ptr<const float>(iX);
+    A.p = bf.ptr<const float>(iP);
+    A.afs = bf.ptr<const float>(iA);
+    A.has_ca = bf.ptr<const unsigned char>(iC);
     A.afs_thr = afs_thr; A.p_thr = p_thr; A.s_star = sqrt_threshold(d_thr);
-    A.patch_of = dev ? patch_of : (int*)(w + oPo);
-    A.n_patches = dev ? n_patches : (int*)(w + oNp);
-    A.patch_size = dev ? patch_size : (int*)(w + oPs);
-    A.patch_mean = dev ? patch_mean : (float*)(w + oPm);
-    if (!small.empty()) {
-        PT_TRY(hipFuncSetAttribute((const void*)k_patches_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(k_patches_small, dim3((unsigned)(small.size() * n_sel)), dim3(SMALL_THREADS), smem, stm, A, (const int*)(w + oSmall), cap);
-        PT_TRY(hipGetLastError());
+    A.patch_of = bf.ptr<int>(iPo);
+    A.n_patches = bf.ptr<int>(iNp);
+    A.patch_size = bf.ptr<int>(iPs);
+    A.patch_mean = bf.ptr<float>(iPm);
+    if (rc == 0 && !small.empty()) {
+        const size_t smem = (size_t)cap * 5 * 4;
+        rc = hip_ok(hipFuncSetAttribute((const void*)k_patches_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), "interface_patches");
+        if (rc == 0)
+            hipLaunchKernelGGL(k_patches_small, dim3((unsigned)(small.size() * n_sel)), dim3(SMALL_THREADS), smem, bf.stm, A, bf.ptr<const int>(iSmall), cap);
     }
-    if (n_items) {
-        int* g = (int*)(w + oG);
+    if (rc == 0 && n_items) {
+        int* g = bf.ptr<int>(iG);
         const size_t L = (size_t)rows_large;
-        const LargeItem* it = (const LargeItem*)(w + oItems);
-        int* nn = (int*)(w + oN);
-        hipLaunchKernelGGL(k_patches_large_gather, dim3((unsigned)n_items), dim3(LARGE_THREADS), 0, stm, A, it, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, nn);
-        PT_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_patches_large_pairs, dim3((unsigned)blk_off.back()), dim3(TILE), 0, stm, (int)n_items, it, (const int*)(w + oBlk), nn,
+        const LargeItem* it = bf.ptr<const LargeItem>(iItems);
+        int* nn = bf.ptr<int>(iN);
+        hipLaunchKernelGGL(k_patches_large_gather, dim3((unsigned)n_items), dim3(LARGE_THREADS), 0, bf.stm, A, it, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, nn);
+        hipLaunchKernelGGL(k_patches_large_pairs, dim3((unsigned)blk_off.back()), dim3(TILE), 0, bf.stm, (int)n_items, it, bf.ptr<const int>(iBlk), nn,
                            g, g + L, g + 2 * L, g + 3 * L, A.s_star);
-        PT_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_patches_large_finish, dim3((unsigned)n_items), dim3(LARGE_THREADS), 0, stm, A, it, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, nn);
-        PT_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_patches_large_finish, dim3((unsigned)n_items), dim3(LARGE_THREADS), 0, bf.stm, A, it, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, nn);
     }
-    if (!dev) {
-        PT_TRY(hipMemcpyAsync(patch_of, w + oPo, n_out * 4, hipMemcpyDeviceToHost, stm));
-        PT_TRY(hipMemcpyAsync(n_patches, w + oNp, (size_t)n_struct * n_sel * 4, hipMemcpyDeviceToHost, stm));
-        PT_TRY(hipMemcpyAsync(patch_size, w + oPs, n_out * 4, hipMemcpyDeviceToHost, stm));
-        PT_TRY(hipMemcpyAsync(patch_mean, w + oPm, n_out * 8, hipMemcpyDeviceToHost, stm));
-    }
-done:
-    (void)hipFreeAsync(w, stm);
-    if (hipStreamSynchronize(stm) != hipSuccess && rc == 0) rc = pfail(PESTO_ERR_HIP, "interface_patches: stream synchronisation failed");
-    return rc;
+    return bf.finish(rc, "interface_patches");
 }

@@ -31,19 +31,14 @@
 // (x, y, z, R^2) in LDS, lane = points lane + 64 m, broadcast reads, ballot exit); areas and group sums in double.
 // Developer hook: the environment variable PESTO_SASA_DEBUG is read per call, bit 0 = stop after the grid build (timing), bit 1 = do not
 // try the lane's last occluder first (timing of that choice; the results do not depend on it).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
 #include <vector>
 
-#include "../../include/pesto_hip.h"
+#include "pesto_call.h"
+#include "pesto_cellgrid.h"      // struct_of and the one-workgroup scan; the grid here is its own (double, per frame, finite atoms only)
 
 namespace pesto {
 
@@ -60,12 +55,6 @@ struct SasaGrid { double minx, miny, minz, inv_h; int nx, ny, nz, any; };
 
 __device__ __forceinline__ bool finite4(float x, float y, float z, float r) {
     return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX && fabsf(r) <= FLT_MAX;
-}
-
-__device__ __forceinline__ int struct_of(int i, int n_struct, const int* __restrict__ offsets) {
-    int lo = 0, hi = n_struct;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
 }
 
 __device__ __forceinline__ int cell_axis(double x, double mn, double inv_h, int n) { return min(n - 1, max(0, (int)((x - mn) * inv_h))); }
@@ -168,26 +157,11 @@ __global__ __launch_bounds__(NT) void k_sasa_count(size_t total, int n_struct, i
 // exclusive scan of the cell counts of one (frame, structure): cnt -> first slot of each cell (and the total behind the last), cursor copy
 __global__ __launch_bounds__(NT) void k_sasa_scan(int n_struct, const int* __restrict__ capoff, int total_cap, const SasaGrid* __restrict__ grids,
                                                   int* __restrict__ cell_cnt, int* __restrict__ cell_cur) {
-    __shared__ int part[NT];
     const int g = blockIdx.x, f = g / n_struct, s = g % n_struct;
     const int nc = grids[g].nx * grids[g].ny * grids[g].nz;
     int* cnt = cell_cnt + (size_t)f * total_cap + capoff[s];
-    int* cur = cell_cur + (size_t)f * total_cap + capoff[s];
-    const int per = (nc + NT - 1) / NT;
-    const int c0 = min(nc, (int)threadIdx.x * per), c1 = min(nc, c0 + per);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += cnt[c];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < NT; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - sum;
-    for (int c = c0; c < c1; ++c) { const int n = cnt[c]; cnt[c] = run; cur[c] = run; run += n; }
-    if (threadIdx.x == NT - 1) cnt[nc] = part[NT - 1];
+    const int total = block_scan_exclusive<NT, true>(cnt, nc, cell_cur + (size_t)f * total_cap + capoff[s]);
+    if (threadIdx.x == NT - 1) cnt[nc] = total;
 }
 
 // (x, y, z, R) records in cell order; the order inside a cell is that of the atomics and may vary, which no result depends on
@@ -357,73 +331,7 @@ __global__ __launch_bounds__(NT) void k_sasa_groups(size_t total, int n_total, i
     out[k] = (float)sum;
 }
 
-// ---- host side (the conventions of the trajectory group: see pesto_trajectory.hip)
-thread_local std::string g_sasa_err;
-
-int sfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_sasa_err = buf;
-    return code;
-}
-
-// the buffers of one call: inputs and outputs are the caller's own pointers on the device side and staged copies on the host side;
-// scratch and host-made tables always live in the call's stream-ordered allocation
-struct Buffers {
-    struct Item { const void* in; void* out; size_t bytes, at; bool own; };
-    bool dev;
-    hipStream_t stm;
-    char* w = nullptr;
-    size_t total = 0;
-    std::vector<Item> items;
-    Buffers(bool dev_, hipStream_t s) : dev(dev_), stm(s) {}
-    int add(const void* in, void* out, size_t bytes, bool own) {
-        Item it{in, out, bytes, total, own};
-        if (own) total += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-        items.push_back(it);
-        return (int)items.size() - 1;
-    }
-    int input(const void* p, size_t bytes) { return add(p, nullptr, bytes, !dev && p); }
-    int table(const void* host, size_t bytes) { return add(host, nullptr, bytes, true); }
-    int output(void* p, size_t bytes) { return add(nullptr, p, bytes, !dev && p); }
-    int scratch(size_t bytes) { return add(nullptr, nullptr, bytes, true); }
-    template <class T> T* ptr(int i) const {
-        const Item& it = items[i];
-        if (it.own) return (T*)(w + it.at);
-        return (T*)(it.in ? it.in : it.out);
-    }
-    int upload() {
-        if (hipMallocAsync((void**)&w, std::max<size_t>(total, 256), stm) != hipSuccess) {
-            w = nullptr;
-            return sfail(PESTO_ERR_NOMEM, "device allocation of %zu bytes failed", total);
-        }
-        for (const Item& it : items)
-            if (it.own && it.in) {
-                hipError_t e = hipMemcpyAsync(w + it.at, it.in, it.bytes, hipMemcpyHostToDevice, stm);
-                if (e != hipSuccess) return sfail(PESTO_ERR_HIP, "copy to the device failed: %s", hipGetErrorString(e));
-            }
-        return 0;
-    }
-    int finish(int rc, const char* what) {
-        if (rc == 0) {
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) rc = sfail(PESTO_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-        }
-        if (rc == 0)
-            for (const Item& it : items)
-                if (it.own && it.out) {
-                    hipError_t e = hipMemcpyAsync(it.out, w + it.at, it.bytes, hipMemcpyDeviceToHost, stm);
-                    if (e != hipSuccess) { rc = sfail(PESTO_ERR_HIP, "%s: copy to the host failed: %s", what, hipGetErrorString(e)); break; }
-                }
-        if (w) (void)hipFreeAsync(w, stm);
-        if (hipStreamSynchronize(stm) != hipSuccess && rc == 0) rc = sfail(PESTO_ERR_HIP, "%s: stream synchronisation failed", what);
-        return rc;
-    }
-};
-
+// ---- host side
 unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
 
 }  // namespace
@@ -431,29 +339,25 @@ unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
 
 using namespace pesto;
 
-const char* pesto_sasa_last_error(void) { return g_sasa_err.c_str(); }
+const char* pesto_sasa_last_error(void) { return last_error(); }
 
 int pesto_sasa(pesto_model* m, int64_t F, int64_t n_total, int32_t n_struct, const int32_t* struct_offsets, const float* X, const float* radius,
                int32_t P, const float* points, double c0, int32_t* counts_out, float* area_out, int32_t n_groups, const int32_t* perm,
                const int32_t* group_off, float* group_out, int32_t ptr_kind, void* stream) {
-    if (!struct_offsets || !X || !radius || !points) return sfail(PESTO_ERR_INVALID, "bad arguments");
-    if (!counts_out && !area_out && !group_out) return sfail(PESTO_ERR_INVALID, "no output requested");
-    if (P < 1 || P > PESTO_SASA_MAX_POINTS) return sfail(PESTO_ERR_INVALID, "1 to %d sphere points, got %d", PESTO_SASA_MAX_POINTS, P);
+    if (!struct_offsets || !X || !radius || !points) return fail(PESTO_ERR_INVALID, "bad arguments");
+    if (!counts_out && !area_out && !group_out) return fail(PESTO_ERR_INVALID, "no output requested");
+    if (P < 1 || P > PESTO_SASA_MAX_POINTS) return fail(PESTO_ERR_INVALID, "1 to %d sphere points, got %d", PESTO_SASA_MAX_POINTS, P);
     if (F < 1 || n_total < 1 || F > 0x7fffffff || n_total > 0x7fffffff || F * n_total > 0x7fffffff)
-        return sfail(PESTO_ERR_INVALID, "F * n_total must be in 1 .. 2^31 - 1 (F = %lld, n_total = %lld)", (long long)F, (long long)n_total);
+        return fail(PESTO_ERR_INVALID, "F * n_total must be in 1 .. 2^31 - 1 (F = %lld, n_total = %lld)", (long long)F, (long long)n_total);
     if (n_struct < 1 || n_struct > n_total || struct_offsets[0] != 0 || struct_offsets[n_struct] != n_total)
-        return sfail(PESTO_ERR_INVALID, "1 <= n_struct <= n_total structures whose offsets run from 0 to n_total");
-    for (int s = 0; s < n_struct; ++s)
-        if (struct_offsets[s + 1] <= struct_offsets[s]) return sfail(PESTO_ERR_INVALID, "struct_offsets must increase strictly (structure %d)", s);
-    if (!std::isfinite(c0)) return sfail(PESTO_ERR_INVALID, "c0 must be finite");
+        return fail(PESTO_ERR_INVALID, "1 <= n_struct <= n_total structures whose offsets run from 0 to n_total");
+    if (const int s = first_unordered(struct_offsets, n_struct); s >= 0)
+        return fail(PESTO_ERR_INVALID, "struct_offsets must increase strictly (structure %d)", s);
+    if (!std::isfinite(c0)) return fail(PESTO_ERR_INVALID, "c0 must be finite");
     if (group_out && (n_groups < 1 || !perm || !group_off || F * (int64_t)n_groups > 0x7fffffff))
-        return sfail(PESTO_ERR_INVALID, "group sums need perm, group_off and 1 <= n_groups with F * n_groups < 2^31");
-    if (F * (int64_t)n_struct > 0x7fffffff) return sfail(PESTO_ERR_INVALID, "F * n_struct must stay below 2^31");
-    if (ptr_kind != PESTO_PTR_HOST && ptr_kind != PESTO_PTR_DEVICE) return sfail(PESTO_ERR_INVALID, "ptr_kind must be PESTO_PTR_HOST or PESTO_PTR_DEVICE");
-    if (int rc = pesto_synchronize(m)) {
-        const char* e = pesto_last_error();
-        return sfail(rc, "%s", e ? e : "invalid model handle");
-    }
+        return fail(PESTO_ERR_INVALID, "group sums need perm, group_off and 1 <= n_groups with F * n_groups < 2^31");
+    if (F * (int64_t)n_struct > 0x7fffffff) return fail(PESTO_ERR_INVALID, "F * n_struct must stay below 2^31");
+    if (int rc = begin(m, ptr_kind)) return rc;
     const char* dbg_env = std::getenv("PESTO_SASA_DEBUG");
     const int dbg = dbg_env ? std::atoi(dbg_env) : 0;
     // cells of a (frame, structure): at most its atoms and MAX_CELLS, plus the total behind the last cell
@@ -462,7 +366,7 @@ int pesto_sasa(pesto_model* m, int64_t F, int64_t n_total, int32_t n_struct, con
         capoff[s + 1] = capoff[s] + std::min<int32_t>(struct_offsets[s + 1] - struct_offsets[s], MAX_CELLS) + 1;
     const int total_cap = capoff[n_struct];                  // <= 2 n_total
     const size_t total = (size_t)F * n_total, n_grids = (size_t)F * n_struct, n_cells = (size_t)F * total_cap;
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    Buffers bf(ptr_kind, stream);
     const int iX = bf.input(X, total * 12), iR = bf.input(radius, (size_t)n_total * 4), iS = bf.input(points, (size_t)P * 12);
     const int iO = bf.table(struct_offsets, ((size_t)n_struct + 1) * 4), iK = bf.table(capoff.data(), capoff.size() * 4);
     const int iC = counts_out ? bf.output(counts_out, total * 4) : bf.scratch(total * 4);

@@ -2,8 +2,7 @@
 // distribution, per-frame log-likelihood, KL divergence), residue contact maps and native contacts, superposition / RMSD and residue
 // centroids of every frame of a trajectory.
 //
-// The C entry points (include/pesto_hip.h) live here too. Like the evaluation group they need only the handle's device
-// (pesto_synchronize sets it) and allocate their buffers stream-ordered per call, so they share nothing with the forward's workspace.
+// The C entry points (include/pesto_hip.h) live here too, on the call plumbing of pesto_call.h.
 //
 // Distances are NumPy's / torch's float32 ones: d = sqrt_rn((dx*dx + dy*dy) + dz*dz), every operation rounded. No kernel takes the square
 // root: sqrt_rn is monotonic, so every comparison of d against a bound is made on the rounded sum s against the smallest float s_star whose
@@ -11,17 +10,12 @@
 // replaced by the smallest float32 not below it, which decides d >= e and d < e exactly for every float32 d.
 // Every floating-point reduction runs in double in a fixed order (strided per thread, a fixed butterfly per wave, the waves in turn), and
 // partial counts are combined as integers, so every output is bit-identical from call to call.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "../../include/pesto_hip.h"
+#include "pesto_call.h"
 
 namespace pesto {
 
@@ -429,81 +423,6 @@ __global__ __launch_bounds__(NT) void k_residue_centroids(size_t total, int N, i
 }
 
 // ---- host side
-thread_local std::string g_traj_err;
-
-int tfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_traj_err = buf;
-    return code;
-}
-
-// the buffers of one call: inputs and outputs are the caller's own pointers on the device side and staged copies on the host side;
-// scratch and host-made tables always live in the call's stream-ordered allocation
-struct Buffers {
-    struct Item { const void* in; void* out; size_t bytes, at; bool own; };
-    bool dev;
-    hipStream_t stm;
-    char* w = nullptr;
-    size_t total = 0;
-    std::vector<Item> items;
-    Buffers(bool dev_, hipStream_t s) : dev(dev_), stm(s) {}
-    int add(const void* in, void* out, size_t bytes, bool own) {
-        Item it{in, out, bytes, total, own};
-        if (own) total += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-        items.push_back(it);
-        return (int)items.size() - 1;
-    }
-    int input(const void* p, size_t bytes) { return add(p, nullptr, bytes, !dev && p); }
-    int table(const void* host, size_t bytes) { return add(host, nullptr, bytes, true); }
-    int output(void* p, size_t bytes) { return add(nullptr, p, bytes, !dev && p); }
-    int scratch(size_t bytes) { return add(nullptr, nullptr, bytes, true); }
-    template <class T> T* ptr(int i) const {
-        const Item& it = items[i];
-        if (it.own) return (T*)(w + it.at);
-        return (T*)(it.in ? it.in : it.out);
-    }
-    int upload() {
-        if (hipMallocAsync((void**)&w, std::max<size_t>(total, 256), stm) != hipSuccess) {
-            w = nullptr;
-            return tfail(PESTO_ERR_NOMEM, "device allocation of %zu bytes failed", total);
-        }
-        for (const Item& it : items)
-            if (it.own && it.in) {
-                hipError_t e = hipMemcpyAsync(w + it.at, it.in, it.bytes, hipMemcpyHostToDevice, stm);
-                if (e != hipSuccess) return tfail(PESTO_ERR_HIP, "copy to the device failed: %s", hipGetErrorString(e));
-            }
-        return 0;
-    }
-    int finish(int rc, const char* what) {
-        if (rc == 0) {
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) rc = tfail(PESTO_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-        }
-        if (rc == 0)
-            for (const Item& it : items)
-                if (it.own && it.out) {
-                    hipError_t e = hipMemcpyAsync(it.out, w + it.at, it.bytes, hipMemcpyDeviceToHost, stm);
-                    if (e != hipSuccess) { rc = tfail(PESTO_ERR_HIP, "%s: copy to the host failed: %s", what, hipGetErrorString(e)); break; }
-                }
-        if (w) (void)hipFreeAsync(w, stm);
-        if (hipStreamSynchronize(stm) != hipSuccess && rc == 0) rc = tfail(PESTO_ERR_HIP, "%s: stream synchronisation failed", what);
-        return rc;
-    }
-};
-
-int begin(pesto_model* m, int32_t ptr_kind) {
-    if (ptr_kind != PESTO_PTR_HOST && ptr_kind != PESTO_PTR_DEVICE) return tfail(PESTO_ERR_INVALID, "ptr_kind must be PESTO_PTR_HOST or PESTO_PTR_DEVICE");
-    if (int rc = pesto_synchronize(m)) {
-        const char* e = pesto_last_error();
-        return tfail(rc, "%s", e ? e : "invalid model handle");
-    }
-    return 0;
-}
-
 float from_bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
 // smallest non-negative float s (+inf if none) for which pred(s) holds; pred must be monotonic (false ... false true ... true) over
@@ -529,8 +448,8 @@ int edge_thresholds(int B, const double* edges, std::vector<float>& sq) {
     sq.resize((size_t)B + 1);
     for (int b = 0; b <= B; ++b) {
         const double e = edges[b];
-        if (!std::isfinite(e) || std::fabs(e) > 3.4028234663852886e38) return tfail(PESTO_ERR_INVALID, "bins[%d] is not a finite float32-range edge", b);
-        if (b && !(edges[b] > edges[b - 1])) return tfail(PESTO_ERR_INVALID, "bins must increase strictly (bins[%d])", b);
+        if (!std::isfinite(e) || std::fabs(e) > 3.4028234663852886e38) return fail(PESTO_ERR_INVALID, "bins[%d] is not a finite float32-range edge", b);
+        if (b && !(edges[b] > edges[b - 1])) return fail(PESTO_ERR_INVALID, "bins must increase strictly (bins[%d])", b);
         float e32 = (float)e;               // round to nearest, then up to the smallest float32 not below e
         if ((double)e32 < e) e32 = std::nextafter(e32, INFINITY);
         sq[b] = first_true([e32](float s) { return sqrt_rn(s) >= e32; });
@@ -539,10 +458,10 @@ int edge_thresholds(int B, const double* edges, std::vector<float>& sq) {
 }
 
 int check_pairs(int64_t F, int64_t Na, int64_t Nb, int B) {
-    if (F < 1 || F > PESTO_TRAJECTORY_MAX_FRAMES) return tfail(PESTO_ERR_INVALID, "1 to 2^24 frames, got %lld", (long long)F);
-    if (B < 1 || B > PESTO_TRAJECTORY_MAX_BINS) return tfail(PESTO_ERR_INVALID, "1 to %d bins, got %d", PESTO_TRAJECTORY_MAX_BINS, B);
+    if (F < 1 || F > PESTO_TRAJECTORY_MAX_FRAMES) return fail(PESTO_ERR_INVALID, "1 to 2^24 frames, got %lld", (long long)F);
+    if (B < 1 || B > PESTO_TRAJECTORY_MAX_BINS) return fail(PESTO_ERR_INVALID, "1 to %d bins, got %d", PESTO_TRAJECTORY_MAX_BINS, B);
     if (Na < 1 || Nb < 1 || Na > 0x7fffffff || Nb > 0x7fffffff || Na * Nb > 0x7fffffff || Na * Nb * B > 0x7fffffff)
-        return tfail(PESTO_ERR_INVALID, "Na * Nb * bins must be in 1 .. 2^31 - 1 (Na = %lld, Nb = %lld)", (long long)Na, (long long)Nb);
+        return fail(PESTO_ERR_INVALID, "Na * Nb * bins must be in 1 .. 2^31 - 1 (Na = %lld, Nb = %lld)", (long long)Na, (long long)Nb);
     return 0;
 }
 
@@ -551,13 +470,13 @@ int check_pairs(int64_t F, int64_t Na, int64_t Nb, int B) {
 
 using namespace pesto;
 
-const char* pesto_trajectory_last_error(void) { return g_traj_err.c_str(); }
+const char* pesto_trajectory_last_error(void) { return last_error(); }
 
 int pesto_contact_counts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, const float* xyz_a, const float* xyz_b, int32_t n_bins,
                          const double* edges, uint32_t* counts_out, float* P_out, int32_t frame_splits, int32_t ptr_kind, void* stream) {
-    if (!xyz_a || !xyz_b || !edges || !counts_out) return tfail(PESTO_ERR_INVALID, "bad arguments");
+    if (!xyz_a || !xyz_b || !edges || !counts_out) return fail(PESTO_ERR_INVALID, "bad arguments");
     if (int rc = check_pairs(F, Na, Nb, n_bins)) return rc;
-    if (frame_splits < 0) return tfail(PESTO_ERR_INVALID, "frame_splits must be 0 (chosen per call) or positive");
+    if (frame_splits < 0) return fail(PESTO_ERR_INVALID, "frame_splits must be 0 (chosen per call) or positive");
     std::vector<float> sq;
     if (int rc = edge_thresholds(n_bins, edges, sq)) return rc;
     if (int rc = begin(m, ptr_kind)) return rc;
@@ -569,8 +488,8 @@ int pesto_contact_counts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
     splits = std::max<int64_t>(1, std::min(splits, chunks));
     const int64_t per_split = (chunks + splits - 1) / splits * CF;
     splits = (F + per_split - 1) / per_split;
-    if (tiles * splits > 0x7fffffff) return tfail(PESTO_ERR_INVALID, "too many workgroups (%lld tiles x %lld frame splits)", (long long)tiles, (long long)splits);
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    if (tiles * splits > 0x7fffffff) return fail(PESTO_ERR_INVALID, "too many workgroups (%lld tiles x %lld frame splits)", (long long)tiles, (long long)splits);
+    Buffers bf(ptr_kind, stream);
     const size_t n_out = (size_t)(Na * Nb) * B;
     const int iA = bf.input(xyz_a, (size_t)F * Na * 12), iB = xyz_b == xyz_a ? iA : bf.input(xyz_b, (size_t)F * Nb * 12);
     const int iS = bf.table(sq.data(), sq.size() * 4), iC = bf.output(counts_out, n_out * 4), iP = bf.output(P_out, n_out * 4);
@@ -581,8 +500,7 @@ int pesto_contact_counts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
         unsigned* cnt = bf.ptr<unsigned>(iC);
         hipError_t e = hipFuncSetAttribute((const void*)k_contact_counts, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e == hipSuccess && splits > 1) e = hipMemsetAsync(cnt, 0, n_out * 4, bf.stm);
-        if (e != hipSuccess) rc = tfail(PESTO_ERR_HIP, "contact_counts: %s", hipGetErrorString(e));
-        else {
+        if ((rc = hip_ok(e, "contact_counts")) == 0) {
             hipLaunchKernelGGL(k_contact_counts, dim3((unsigned)(tiles * splits)), dim3(NT), smem, bf.stm, (int)F, (int)Na, (int)Nb,
                                bf.ptr<const float>(iA), bf.ptr<const float>(iB), B, top, bf.ptr<const float>(iS), cnt, (int)tiles_j, (int)tiles, (int)splits,
                                (int)per_split);
@@ -596,7 +514,7 @@ int pesto_contact_counts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
 
 int pesto_contact_loglik(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, const float* xyz_a, const float* xyz_b, int32_t n_bins,
                          const double* edges, const float* P, float* L_out, int32_t ptr_kind, void* stream) {
-    if (!xyz_a || !xyz_b || !edges || !P || !L_out) return tfail(PESTO_ERR_INVALID, "bad arguments");
+    if (!xyz_a || !xyz_b || !edges || !P || !L_out) return fail(PESTO_ERR_INVALID, "bad arguments");
     if (int rc = check_pairs(F, Na, Nb, n_bins)) return rc;
     std::vector<float> sq;
     if (int rc = edge_thresholds(n_bins, edges, sq)) return rc;
@@ -606,8 +524,8 @@ int pesto_contact_loglik(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
     // the tiles' partials (one double per tile and frame) live in a scratch of at most LOGLIK_SCRATCH bytes (or one LF-frame chunk, if
     // that is larger): the frames go through the two kernels in passes of `pass` frames, whatever F is
     const int64_t pass = std::min<int64_t>((F + LF - 1) / LF * LF, std::max<int64_t>(LF, LOGLIK_SCRATCH / (tiles * 8) / LF * LF));
-    if (tiles * (pass / LF) > 0x7fffffff) return tfail(PESTO_ERR_INVALID, "too many workgroups (%lld tiles)", (long long)tiles);
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    if (tiles * (pass / LF) > 0x7fffffff) return fail(PESTO_ERR_INVALID, "too many workgroups (%lld tiles)", (long long)tiles);
+    Buffers bf(ptr_kind, stream);
     const int iA = bf.input(xyz_a, (size_t)F * Na * 12), iB = xyz_b == xyz_a ? iA : bf.input(xyz_b, (size_t)F * Nb * 12);
     const int iS = bf.table(sq.data(), sq.size() * 4), iP = bf.input(P, (size_t)(Na * Nb) * B * 4), iL = bf.output(L_out, (size_t)F * 4);
     const int iW = bf.scratch((size_t)tiles * pass * 8);
@@ -615,8 +533,7 @@ int pesto_contact_loglik(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
     if (rc == 0) {
         const int top = pow2_floor(B);
         const size_t smem = (2 * (size_t)LT * 3 * LPAD + 2 * (size_t)top) * 4;
-        hipError_t e = hipFuncSetAttribute((const void*)k_contact_loglik, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) rc = tfail(PESTO_ERR_HIP, "contact_loglik: %s", hipGetErrorString(e));
+        rc = hip_ok(hipFuncSetAttribute((const void*)k_contact_loglik, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), "contact_loglik");
         for (int64_t f0 = 0; rc == 0 && f0 < F; f0 += pass) {
             const int64_t nf = std::min(pass, F - f0), chunks = (nf + LF - 1) / LF;
             hipLaunchKernelGGL(k_contact_loglik, dim3((unsigned)(tiles * chunks)), dim3(NT), smem, bf.stm, (int)nf, (int)Na, (int)Nb,
@@ -631,11 +548,11 @@ int pesto_contact_loglik(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
 
 int pesto_contact_div_kl(pesto_model* m, int64_t n_pairs, int32_t n_bins, const float* P, const float* Q, float* D_out, int32_t ptr_kind,
                          void* stream) {
-    if (!P || !Q || !D_out) return tfail(PESTO_ERR_INVALID, "bad arguments");
+    if (!P || !Q || !D_out) return fail(PESTO_ERR_INVALID, "bad arguments");
     if (n_pairs < 1 || n_bins < 1 || n_pairs > 0x7fffffff || n_pairs * n_bins > 0x7fffffff)
-        return tfail(PESTO_ERR_INVALID, "n_pairs * n_bins must be in 1 .. 2^31 - 1");
+        return fail(PESTO_ERR_INVALID, "n_pairs * n_bins must be in 1 .. 2^31 - 1");
     if (int rc = begin(m, ptr_kind)) return rc;
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    Buffers bf(ptr_kind, stream);
     const size_t n = (size_t)n_pairs * n_bins * 4;
     const int iP = bf.input(P, n), iQ = Q == P ? iP : bf.input(Q, n), iD = bf.output(D_out, (size_t)n_pairs * 4);
     int rc = bf.upload();
@@ -648,27 +565,26 @@ int pesto_contact_div_kl(pesto_model* m, int64_t n_pairs, int32_t n_bins, const 
 int pesto_residue_contact_maps(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, const float* xyz_a, const float* xyz_b, int32_t Ra, int32_t Rb,
                                const int32_t* perm_a, const int32_t* off_a, const int32_t* perm_b, const int32_t* off_b, float r_thr, float scale,
                                uint8_t* maps_out, int32_t ptr_kind, void* stream) {
-    if (!xyz_a || !xyz_b || !perm_a || !off_a || !perm_b || !off_b || !maps_out) return tfail(PESTO_ERR_INVALID, "bad arguments");
+    if (!xyz_a || !xyz_b || !perm_a || !off_a || !perm_b || !off_b || !maps_out) return fail(PESTO_ERR_INVALID, "bad arguments");
     if (F < 1 || F > 0x7fffffff || Na < 1 || Nb < 1 || Na + Nb > PESTO_TRAJECTORY_MAX_MAP_ATOMS)
-        return tfail(PESTO_ERR_INVALID, "F >= 1 frames and 1 <= Na, Nb with Na + Nb <= %d atoms", PESTO_TRAJECTORY_MAX_MAP_ATOMS);
-    if (Ra < 1 || Rb < 1 || Ra > Na || Rb > Nb || (int64_t)Ra * Rb > 0x7fffffff) return tfail(PESTO_ERR_INVALID, "1 <= Ra <= Na and 1 <= Rb <= Nb residues");
-    if (!std::isfinite(r_thr) || !std::isfinite(scale) || !(scale > 0.f)) return tfail(PESTO_ERR_INVALID, "r_thr must be finite and scale positive and finite");
+        return fail(PESTO_ERR_INVALID, "F >= 1 frames and 1 <= Na, Nb with Na + Nb <= %d atoms", PESTO_TRAJECTORY_MAX_MAP_ATOMS);
+    if (Ra < 1 || Rb < 1 || Ra > Na || Rb > Nb || (int64_t)Ra * Rb > 0x7fffffff) return fail(PESTO_ERR_INVALID, "1 <= Ra <= Na and 1 <= Rb <= Nb residues");
+    if (!std::isfinite(r_thr) || !std::isfinite(scale) || !(scale > 0.f)) return fail(PESTO_ERR_INVALID, "r_thr must be finite and scale positive and finite");
     if (int rc = begin(m, ptr_kind)) return rc;
     // contact  <=>  fl(sqrt_rn(s) * scale) < r_thr  <=>  s < s_star (the product is monotonic in s)
     const float s_star = first_true([r_thr, scale](float s) { volatile float d = sqrt_rn(s) * scale; return !(d < r_thr); });
     const int64_t n_pairs = (int64_t)Ra * Rb;
     int64_t ysplit = std::max<int64_t>(1, std::min<int64_t>((n_pairs + NT - 1) / NT, (2048 + F - 1) / F));
-    if (F * ysplit > 0x7fffffff) return tfail(PESTO_ERR_INVALID, "too many workgroups");
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    if (F * ysplit > 0x7fffffff) return fail(PESTO_ERR_INVALID, "too many workgroups");
+    Buffers bf(ptr_kind, stream);
     const int iA = bf.input(xyz_a, (size_t)F * Na * 12), iB = bf.input(xyz_b, (size_t)F * Nb * 12);
     const int iPa = bf.input(perm_a, (size_t)Na * 4), iOa = bf.input(off_a, ((size_t)Ra + 1) * 4), iPb = bf.input(perm_b, (size_t)Nb * 4),
               iOb = bf.input(off_b, ((size_t)Rb + 1) * 4), iM = bf.output(maps_out, (size_t)F * n_pairs);
     int rc = bf.upload();
     if (rc == 0) {
         const size_t smem = (size_t)(Na + Nb) * 12;
-        hipError_t e = hipFuncSetAttribute((const void*)k_residue_maps, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) rc = tfail(PESTO_ERR_HIP, "residue_contact_maps: %s", hipGetErrorString(e));
-        else
+        rc = hip_ok(hipFuncSetAttribute((const void*)k_residue_maps, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), "residue_contact_maps");
+        if (rc == 0)
             hipLaunchKernelGGL(k_residue_maps, dim3((unsigned)(F * ysplit)), dim3(NT), smem, bf.stm, (int)Na, (int)Nb, Ra, Rb, bf.ptr<const float>(iA),
                                bf.ptr<const float>(iB), bf.ptr<const int>(iPa), bf.ptr<const int>(iPb), bf.ptr<const int>(iOa), bf.ptr<const int>(iOb), s_star,
                                bf.ptr<unsigned char>(iM), (int)ysplit);
@@ -678,11 +594,11 @@ int pesto_residue_contact_maps(pesto_model* m, int64_t F, int64_t Na, int64_t Nb
 
 int pesto_native_contacts(pesto_model* m, int64_t F, int64_t F_ref, int64_t n, const uint8_t* maps_ref, const uint8_t* maps, int64_t* native_out,
                           int64_t* ref_total_out, int32_t ptr_kind, void* stream) {
-    if (!maps_ref || !maps || !native_out || !ref_total_out) return tfail(PESTO_ERR_INVALID, "bad arguments");
+    if (!maps_ref || !maps || !native_out || !ref_total_out) return fail(PESTO_ERR_INVALID, "bad arguments");
     if (F < 1 || F > 0x7fffffff || (F_ref != 1 && F_ref != F) || n < 1 || n > 0x7fffffff)
-        return tfail(PESTO_ERR_INVALID, "F >= 1 frames, F_ref = 1 or F, 1 <= n < 2^31 residue pairs");
+        return fail(PESTO_ERR_INVALID, "F >= 1 frames, F_ref = 1 or F, 1 <= n < 2^31 residue pairs");
     if (int rc = begin(m, ptr_kind)) return rc;
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    Buffers bf(ptr_kind, stream);
     const int iR = bf.input(maps_ref, (size_t)F_ref * n), iM = bf.input(maps, (size_t)F * n), iN = bf.output(native_out, (size_t)F * 8),
               iT = bf.output(ref_total_out, 8), iW = bf.scratch((size_t)F_ref * 8);
     int rc = bf.upload();
@@ -699,12 +615,12 @@ int pesto_native_contacts(pesto_model* m, int64_t F, int64_t F_ref, int64_t n, c
 int pesto_superpose(pesto_model* m, int64_t F, int64_t F_ref, int64_t N_ref, int64_t N, int64_t n_sel, const float* xyz_ref, const float* xyz,
                     const int32_t* sel_ref, const int32_t* sel, double scale, float* t_out, float* R_out, float* t_ref_out, float* xyz_out,
                     float* rmsd_out, int32_t ptr_kind, void* stream) {
-    if (!xyz_ref || !xyz || !t_out || !R_out || !t_ref_out || !rmsd_out) return tfail(PESTO_ERR_INVALID, "bad arguments");
+    if (!xyz_ref || !xyz || !t_out || !R_out || !t_ref_out || !rmsd_out) return fail(PESTO_ERR_INVALID, "bad arguments");
     if (F < 1 || F > 0x7fffffff || (F_ref != 1 && F_ref != F) || N < 1 || N_ref < 1 || N > 0x7fffffff || N_ref > 0x7fffffff || n_sel < 3 ||
         (!sel && n_sel != N) || (!sel_ref && n_sel != N_ref) || n_sel > 0x7fffffff)
-        return tfail(PESTO_ERR_INVALID, "F >= 1 frames, F_ref = 1 or F, at least 3 selected atoms on both sides (all atoms without a selection)");
+        return fail(PESTO_ERR_INVALID, "F >= 1 frames, F_ref = 1 or F, at least 3 selected atoms on both sides (all atoms without a selection)");
     if (int rc = begin(m, ptr_kind)) return rc;
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    Buffers bf(ptr_kind, stream);
     const int iY = bf.input(xyz_ref, (size_t)F_ref * N_ref * 12), iX = bf.input(xyz, (size_t)F * N * 12);
     const int iSr = bf.input(sel_ref, (size_t)n_sel * 4), iS = bf.input(sel, (size_t)n_sel * 4);
     const int it = bf.output(t_out, (size_t)F * 12), iR = bf.output(R_out, (size_t)F * 36), itr = bf.output(t_ref_out, (size_t)F_ref * 12),
@@ -725,11 +641,11 @@ int pesto_superpose(pesto_model* m, int64_t F, int64_t F_ref, int64_t N_ref, int
 
 int pesto_residue_centroids(pesto_model* m, int64_t F, int64_t N, int64_t R, const float* X_frames, const int32_t* perm, const int32_t* off,
                             float* out, int32_t ptr_kind, void* stream) {
-    if (!X_frames || !perm || !off || !out) return tfail(PESTO_ERR_INVALID, "bad arguments");
+    if (!X_frames || !perm || !off || !out) return fail(PESTO_ERR_INVALID, "bad arguments");
     if (F < 1 || N < 1 || R < 1 || N > 0x7fffffff || R > 0x7fffffff || F * R > (int64_t)0x7fffffff * NT)
-        return tfail(PESTO_ERR_INVALID, "F, N, R >= 1 and F * R below 2^39");
+        return fail(PESTO_ERR_INVALID, "F, N, R >= 1 and F * R below 2^39");
     if (int rc = begin(m, ptr_kind)) return rc;
-    Buffers bf(ptr_kind == PESTO_PTR_DEVICE, (hipStream_t)stream);
+    Buffers bf(ptr_kind, stream);
     const int iX = bf.input(X_frames, (size_t)F * N * 12), iP = bf.input(perm, (size_t)N * 4), iO = bf.input(off, ((size_t)R + 1) * 4),
               iC = bf.output(out, (size_t)F * R * 12);
     int rc = bf.upload();
