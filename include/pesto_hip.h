@@ -480,6 +480,42 @@ int pesto_sasa(pesto_model* m, int64_t F, int64_t n_total, int32_t n_struct, con
                int32_t P, const float* points, double c0, int32_t* counts_out, float* area_out, int32_t n_groups, const int32_t* perm,
                const int32_t* group_off, float* group_out, int32_t ptr_kind, void* stream);
 
+/* ---- DSSP secondary structure (Kabsch & Sander 1983) ----
+ * replaces: wrapper_secondary_structure (interfaceome/secondary_structures.py:27-31: md.compute_dssp(traj, simplified=False) on one
+ * structure at a time in a 12-process pool). Every frame of a trajectory and every structure of a ragged batch goes through one launch
+ * sequence. Failures are reported through pesto_dssp_last_error() (thread-local; an invalid handle's message is copied there too). Like
+ * the other analysis groups the entry point uses the handle for its device, allocates its buffers stream-ordered per call, keeps no state
+ * between calls and synchronises `stream`; X and the outputs are host or device memory according to ptr_kind; the topology tables (res_offsets, bb_atoms, proline, chain) are
+ * always HOST memory, so their limits are checked before anything is launched.
+ *
+ * Inputs. X float32 [F,n_atoms,3]; scale multiplies the coordinates to angstroms (in double). The residues res_offsets[s] ..
+ * res_offsets[s+1] of the R_total rows form structure s and only meet each other. bb_atoms int32 [R_total,4]: the rows of X that hold
+ * the N, CA, C and O of every residue, -1 for a missing atom (such a residue gets PESTO_DSSP_NA and takes part in nothing). proline
+ * uint8 [R_total]: 1 for a proline (no N-H). chain int32 [R_total]: residues of different chain numbers are never consecutive.
+ * The definition - hydrogen placement, the electrostatic energy in thousandths of kcal/mol, the best-two selection, bridges, ladders and
+ * their bulge links, helices, turns and bends, all in double as written, without fused multiply-adds - is the module docstring of
+ * pesto_amd/dssp.py; pesto_dssp.hip restates it above its kernels. Every output is an integer that depends neither on the other
+ * structures of the launch nor on the order of the threads: bit-identical from call to call.
+ *     codes_out uint8 [F,R_total] or NULL: enum pesto_dssp_code
+ *     partners_out int32 [F,R_total,4] or NULL: per residue its two best acceptors (as N-H donor) and its two best donors (as C=O
+ *         acceptor), as residue indices WITHIN ITS STRUCTURE, best first, -1 for none
+ *     energies_out int32 [F,R_total,4] or NULL: their energies in thousandths of kcal/mol (negative; 0 for none)
+ * at least one of codes_out and the pair partners_out / energies_out (either of the pair may be NULL on its own).
+ * Limits, checked before any launch (PESTO_ERR_INVALID): 1 <= F, 1 <= n_atoms, F * n_atoms < 2^31; 1 <= n_struct, strictly increasing
+ * offsets from 0 to R_total, at most PESTO_DSSP_MAX_RESIDUES per structure, F * R_total < 2^31 and F * n_struct < 2^31; finite scale;
+ * every atom row in -1 .. n_atoms - 1. */
+const char* pesto_dssp_last_error(void);
+
+enum { PESTO_DSSP_MAX_RESIDUES = 65535 };
+enum pesto_dssp_code {
+    PESTO_DSSP_BLANK = 0, PESTO_DSSP_H = 1, PESTO_DSSP_B = 2, PESTO_DSSP_E = 3, PESTO_DSSP_G = 4, PESTO_DSSP_I = 5, PESTO_DSSP_T = 6,
+    PESTO_DSSP_S = 7, PESTO_DSSP_NA = 8
+};
+
+int pesto_dssp(pesto_model* m, int64_t F, int64_t n_atoms, const float* X, double scale, int64_t R_total, int32_t n_struct,
+               const int32_t* res_offsets, const int32_t* bb_atoms, const uint8_t* proline, const int32_t* chain, uint8_t* codes_out,
+               int32_t* partners_out, int32_t* energies_out, int32_t ptr_kind, void* stream);
+
 /* ---- test hooks ----
  * Debug twins of the shipped kernels, selected per handle (the parity tests run every stage through each of them):
  * layer_kernels 0 = shipped (hybrid first layer; arithmetic per the precision policy), 1 = reference-formulation fp32 VALU

@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "pesto_interface_patches", "pesto_patches_last_error", "pesto_contacts", "pesto_contacts_last_error",
     "pesto_trajectory_last_error", "pesto_contact_counts", "pesto_contact_loglik", "pesto_contact_div_kl", "pesto_residue_contact_maps",
     "pesto_native_contacts", "pesto_superpose", "pesto_residue_centroids", "pesto_sasa_last_error", "pesto_sasa",
+    "pesto_dssp_last_error", "pesto_dssp",
 ]
 
 _lib = None
@@ -152,22 +153,25 @@ def load():
     lib.pesto_sasa_last_error.restype = ctypes.c_char_p
     lib.pesto_sasa_last_error.argtypes = []
     lib.pesto_sasa.argtypes = [c_p, i64, i64, i32, c_p, c_p, c_p, i32, c_p, ctypes.c_double, c_p, c_p, i32, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_dssp_last_error.restype = ctypes.c_char_p
+    lib.pesto_dssp_last_error.argtypes = []
+    lib.pesto_dssp.argtypes = [c_p, i64, i64, c_p, ctypes.c_double, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_stage_embed.argtypes = [c_p, i64, c_p, c_p]
     lib.pesto_stage_unpack.argtypes = [c_p, i64, i32, c_p, c_p, i32, c_p, c_p]
     lib.pesto_stage_layer.argtypes = [c_p, i32, c_p, c_p]
     lib.pesto_stage_pool.argtypes = [c_p, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p]
     for name in ABI_SYMBOLS:
         if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error",
-                        "pesto_trajectory_last_error", "pesto_sasa_last_error"):
+                        "pesto_trajectory_last_error", "pesto_sasa_last_error", "pesto_dssp_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are six channels:
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are seven channels:
     pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
-    pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error and pesto_sasa_last_error."""
+    pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error and pesto_dssp_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")

@@ -14,7 +14,8 @@
 //     everybody, itself included, in every comparison.
 // Build: k_grid_setup -> k_grid_count -> k_grid_scan -> k_grid_scatter, four launches; the users differ in what they check per atom in
 // the count pass and in the payload they scatter beside the coordinates, both functors.
-// (pesto_sasa.hip includes this header for struct_of and block_scan_exclusive only: its grid is another one, in double and per frame.)
+// (pesto_sasa.hip includes this header for struct_of and block_scan_exclusive only: its grid is another one, in double and per frame;
+// pesto_dssp.hip likewise: it has no grid.)
 #pragma once
 #include <hip/hip_runtime.h>
 

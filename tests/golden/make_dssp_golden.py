@@ -1,0 +1,538 @@
+#!/usr/bin/env python3
+"""Generate the DSSP golden (tests/golden/dssp.npz) from a loop-level restatement of the definition in pesto_amd/dssp.py's docstring
+(mdtraj is not available, so its output cannot be recorded; the definition is the contract). Everything runs on the CPU, in Python
+floats (IEEE doubles, every operation rounded on its own, math.sqrt), written from the text and not from the kernel.
+
+Every case stores backbone coordinates only (X float32 [F, n_atoms, 3], the N / CA / C / O rows of every residue, proline flags, chain
+numbers, sizes) with the codes, the partner table and the energies in thousandths the restatement gives.
+
+Cases
+  batch    the residues with a backbone atom of 1ZNS, 1H9D (two chains), 1OL5, 6O1T and 7KHT (.pdb1 of tests/golden/pdb, read with the
+           project's reader), one structure each; batch_full_* keeps the tables over ALL residues of the files (what backbone_table gives)
+  frames   8 frames of 1ZNS: a seeded rigid motion plus 0.3 A of Gaussian noise each
+  planted  an ideal alpha helix of 12 residues (phi / psi = -57 / -47; asserted ' ' + 'H' * 10 + ' '), an ideal 3-10 helix, an
+           antiparallel and a parallel pair of strands cropped from the batch, the 1OL5 hairpin with its bulges and the meander it
+           starts (asserted: the turn between the second and the third strand is not E), the helix with a proline / with a C-N bond
+           stretched past 2.5 A / with a residue without O / with a NaN coordinate / cut to 1, 2, 4, 5 and 6 residues, a donor and an
+           acceptor whose CAs are exactly 9.0 A apart (no bond: the test is <) and the same at 8.5 A (bonded), a one-residue structure
+           between two helices, and crops of 6O1T of 127 .. 129 and 255 .. 257 residues (the kernel's tile and workgroup edges)
+  scale10  the batch with float32(X / 10) and scale = 10: the structures whose decisions stay unflagged and whose codes stay equal
+
+Near-threshold decisions. Every comparison of the definition (2.5 A, 9.0 A, 0.5 A, the rounding of 1000 e at .5, cos 70 deg) that falls
+within 1e-6 of its threshold is flagged; the generator asserts that no stored case has one apart from the planted exact 9.0, so the
+GPU's exact comparison does not rest on the last bit of a device sqrt or division.
+
+Agreement with the files' own HELIX / SHEET records (simplified alphabet, residues with all four atoms), measured by this script and
+stored as agreement_*; no test asserts it:
+  1ZNS 0.856   1H9D 0.824   1OL5 0.884   6O1T 0.923   7KHT 0.907;   every SHEET residue is E in all five
+(the last printed run; see the end of main()).
+
+Usage:  python tests/golden/make_dssp_golden.py
+"""
+import gzip
+import math
+import os
+import sys
+
+import numpy as np
+
+OUT = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(OUT))
+sys.path.insert(0, ROOT)
+BATCH = ["1ZNS.pdb1", "1H9D.pdb1", "1OL5.pdb1", "6O1T.pdb1", "7KHT.pdb1"]
+CODES = [" ", "H", "B", "E", "G", "I", "T", "S", "NA"]
+BLANK, H, B, E, G, I, T, S, NA = range(9)
+Q = 27.888
+COS70 = 0.3420201433256687
+EPS = 1e-6
+NAN = float("nan")
+
+
+def dist(a, b):
+    dx, dy, dz = a[0] - b[0], a[1] - b[1], a[2] - b[2]
+    return math.sqrt(dx * dx + dy * dy + dz * dz)
+
+
+def round_away(t):
+    a = abs(t)
+    fl = math.floor(a)
+    r = fl + (1.0 if a - fl >= 0.5 else 0.0)
+    return -r if t < 0 else r
+
+
+def dssp(X, table, pro, chain, scale=1.0, flags=None):
+    """(codes uint8 [R], partners int32 [R, 4], energies int32 [R, 4]) of ONE structure, one frame. X float32 [n_atoms, 3]."""
+    R = len(table)
+    flags = [] if flags is None else flags
+
+    def near(v, thr, what):
+        if abs(v - thr) < EPS:
+            flags.append((what, v))
+
+    def atom(r, k):
+        return [float(X[table[r][k]][c]) * scale for c in range(3)]
+    full = [all(table[r][k] >= 0 for k in range(4)) for r in range(R)]
+    Np = [atom(r, 0) if full[r] else None for r in range(R)]
+    CA = [atom(r, 1) if full[r] else None for r in range(R)]
+    Cp = [atom(r, 2) if full[r] else None for r in range(R)]
+    Op = [atom(r, 3) if full[r] else None for r in range(R)]
+    # continuity
+    cont = [False] * R
+    for i in range(1, R):
+        if full[i - 1] and full[i] and chain[i - 1] == chain[i]:
+            d = dist(Cp[i - 1], Np[i])
+            near(d, 2.5, "cont")
+            cont[i] = d <= 2.5
+    breaks = [0] * R
+    for i in range(1, R):
+        breaks[i] = breaks[i - 1] + (0 if cont[i] else 1)
+
+    def nobreak(a, b):
+        return 0 <= a <= b < R and breaks[b] == breaks[a]
+    # 1. hydrogens
+    Hp = [None] * R
+    for i in range(R):
+        if not full[i]:
+            continue
+        Hp[i] = list(Np[i])
+        if cont[i] and not pro[i]:
+            ln = dist(Cp[i - 1], Op[i - 1])
+            for c in range(3):
+                df = Cp[i - 1][c] - Op[i - 1][c]
+                Hp[i][c] = Np[i][c] + ((df / ln) if ln != 0 else (NAN if df == 0 or df != df else math.copysign(math.inf, df)))
+    # 2. energies and the best two
+    acc = [[] for _ in range(R)]     # acc[d]: (e_m, a)
+    don = [[] for _ in range(R)]     # don[a]: (e_m, d)
+    for d in range(R):
+        if not full[d] or pro[d]:
+            continue
+        for a in range(R):
+            if a == d or a == d - 1 or not full[a]:
+                continue
+            dca = dist(CA[d], CA[a])
+            near(dca, 9.0, "ca")
+            if not dca < 9.0:
+                continue
+            ho, hc, nc, no = dist(Hp[d], Op[a]), dist(Hp[d], Cp[a]), dist(Np[d], Cp[a]), dist(Np[d], Op[a])
+            for v in (ho, hc, nc, no):
+                near(v, 0.5, "short")
+            if ho < 0.5 or hc < 0.5 or nc < 0.5 or no < 0.5:
+                em = -9900
+            else:
+                if min(ho, hc, nc, no) == 0.0:            # (only a NaN beside it reaches here)
+                    continue
+                e = -Q / ho + Q / hc - Q / nc + Q / no
+                t = 1000.0 * e
+                if t != t:
+                    continue
+                if abs(t) < 1e7:
+                    near(abs(t) - math.floor(abs(t)), 0.5, "round")
+                r = round_away(t)
+                if not r < 0:
+                    continue
+                em = int(max(r, -9900.0))
+            acc[d].append((em, a))
+            don[a].append((em, d))
+    partners = np.full((R, 4), -1, np.int32)
+    energies = np.zeros((R, 4), np.int32)
+    for r in range(R):
+        for k, (em, p) in enumerate(sorted(acc[r])[:2]):
+            partners[r, k], energies[r, k] = p, em
+        for k, (em, p) in enumerate(sorted(don[r])[:2]):
+            partners[r, 2 + k], energies[r, 2 + k] = p, em
+
+    best = [sorted(acc[r])[:2] for r in range(R)]
+
+    def bond(d, a):
+        if not (0 <= d < R and 0 <= a < R):
+            return False
+        return any(p == a and em < -500 for em, p in best[d])
+    # 3. bridges
+    ok3 = [nobreak(i - 1, i + 1) for i in range(R)]
+    bridges = {}
+    for i in range(1, R):
+        if not ok3[i]:
+            continue
+        for j in range(i + 3, R - 1):
+            if not ok3[j]:
+                continue
+            if (bond(i + 1, j) and bond(j, i - 1)) or (bond(j + 1, i) and bond(i, j - 1)):
+                bridges[(i, j)] = "P"
+            elif (bond(i + 1, j - 1) and bond(j + 1, i - 1)) or (bond(j, i) and bond(i, j)):
+                bridges[(i, j)] = "A"
+    # 4. ladders: maximal runs; [type, i_begin, i_end, j_begin (smallest j), j_end (largest j), bridges]
+    ladders = []
+    for (i, j), t in sorted(bridges.items()):
+        step = 1 if t == "P" else -1
+        if bridges.get((i - 1, j - step)) == t:
+            continue
+        n = 1
+        while bridges.get((i + n, j + step * n)) == t:
+            n += 1
+        j2 = j + step * (n - 1)
+        ladders.append([t, i, i + n - 1, min(j, j2), max(j, j2), n])
+    root = list(range(len(ladders)))
+
+    def find(x):
+        while root[x] != x:
+            x = root[x]
+        return x
+    for a, A in enumerate(ladders):
+        for b, Bl in enumerate(ladders):
+            if a == b or A[0] != Bl[0]:
+                continue
+            gi = Bl[1] - A[2] - 1
+            if A[0] == "P":
+                gj, unbroken = Bl[3] - A[4] - 1, nobreak(A[4], Bl[3])
+            else:
+                gj, unbroken = A[3] - Bl[4] - 1, nobreak(Bl[4], A[3])
+            if gi >= 0 and gj >= 0 and ((gi <= 1 and gj <= 4) or (gj <= 1 and gi <= 4)) and nobreak(A[2], Bl[1]) and unbroken:
+                root[find(a)] = find(b)
+    sheet = [BLANK] * R
+    groups = {}
+    for k, L in enumerate(ladders):
+        g = groups.setdefault(find(k), [L[1], L[2], L[3], L[4], 0])
+        g[0], g[1], g[2], g[3], g[4] = min(g[0], L[1]), max(g[1], L[2]), min(g[2], L[3]), max(g[3], L[4]), g[4] + L[5]
+    for want in (B, E):
+        for g in groups.values():
+            if (E if g[4] > 1 else B) == want:
+                for r in list(range(g[0], g[1] + 1)) + list(range(g[2], g[3] + 1)):
+                    if sheet[r] != E:
+                        sheet[r] = want
+    # 5. helices, turns, bends
+    def start(n, i):
+        return nobreak(i, i + n) and bond(i + n, i)
+    code = list(sheet)
+    for i in range(1, R):
+        if start(4, i - 1) and start(4, i):
+            for r in range(i, i + 4):
+                code[r] = H
+    for n, c in ((3, G), (5, I)):
+        for i in range(1, R):
+            if start(n, i - 1) and start(n, i) and all(code[r] in (BLANK, c) for r in range(i, i + n)):
+                for r in range(i, i + n):
+                    code[r] = c
+    for i in range(1, R - 1):
+        if code[i] != BLANK:
+            continue
+        if any(start(n, i - k) for n in (3, 4, 5) for k in range(1, n)):
+            code[i] = T
+        elif nobreak(i - 2, i + 2):
+            u = [CA[i][c] - CA[i - 2][c] for c in range(3)]
+            v = [CA[i + 2][c] - CA[i][c] for c in range(3)]
+            uv = u[0] * v[0] + u[1] * v[1] + u[2] * v[2]
+            uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2]
+            vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2]
+            den = math.sqrt(uu * vv)
+            cosk = uv / den if den != 0 else NAN
+            near(cosk, COS70, "bend")
+            if cosk < COS70:
+                code[i] = S
+    for r in range(R):
+        if not full[r]:
+            code[r] = NA
+    return np.array(code, np.uint8), partners, energies
+
+
+def text(codes):
+    return "".join(CODES[c] if c != NA else "?" for c in codes)
+
+
+# ---------------------------------------------------------------- inputs
+def residue_table(d):
+    """(table [R, 4] of atom rows, proline [R], chain number [R], key [R] = (chain_name, resid)) of a reader's dict: residues are runs of
+    atoms with one (chain_name, resid, resname, icode); chains are numbered in order of first appearance; the first atom of a name counts."""
+    n = len(d["resid"])
+    icode = d.get("icode")
+    table, pro, chain, keys, chains, last = [], [], [], [], {}, None
+    for a in range(n):
+        key = (str(d["chain_name"][a]), int(d["resid"][a]), str(d["resname"][a]), "" if icode is None else str(icode[a]))
+        if key != last:
+            table.append([-1, -1, -1, -1])
+            pro.append(1 if key[2].strip() == "PRO" else 0)
+            chain.append(chains.setdefault(key[0], len(chains)))
+            keys.append((key[0], key[1]))
+            last = key
+        name = str(d["name"][a]).strip()
+        if name in ("N", "CA", "C", "O"):
+            k = ("N", "CA", "C", "O").index(name)
+            if table[-1][k] < 0:
+                table[-1][k] = a
+    return np.array(table, np.int32).reshape(-1, 4), np.array(pro, np.uint8), np.array(chain, np.int32), keys
+
+
+def compact(xyz, table, pro, chain, keep):
+    """backbone-only copy of the residues `keep`: (X float32 [n, 3], table)"""
+    rows, tab = [], []
+    for r in keep:
+        t = []
+        for k in range(4):
+            if table[r][k] >= 0:
+                t.append(len(rows))
+                rows.append(xyz[table[r][k]])
+            else:
+                t.append(-1)
+        tab.append(t)
+    return np.array(rows, np.float32).reshape(-1, 3), np.array(tab, np.int32).reshape(-1, 4), pro[keep].copy(), chain[keep].copy()
+
+
+def place(a, b, c, bond, angle, tors):
+    a, b, c = np.asarray(a, float), np.asarray(b, float), np.asarray(c, float)
+    bc = (c - b) / np.linalg.norm(c - b)
+    n = np.cross(b - a, bc)
+    n /= np.linalg.norm(n)
+    m = np.cross(n, bc)
+    ang, tor = math.radians(angle), math.radians(tors)
+    return c + (-bond * math.cos(ang)) * bc + (bond * math.sin(ang) * math.cos(tor)) * m + (bond * math.sin(ang) * math.sin(tor)) * n
+
+
+def ideal(n, phi, psi):
+    """float32 [4 n, 3]: N, CA, C, O of n residues with the given backbone torsions, omega = 180 (Engh & Huber bond geometry)"""
+    Ns, CAs, Cs, Os = [np.array([0.0, 0.0, 0.0])], [np.array([1.458, 0.0, 0.0])], [], []
+    Cs.append(np.array([1.458 - 1.525 * math.cos(math.radians(111.0)), 1.525 * math.sin(math.radians(111.0)), 0.0]))
+    for i in range(n):
+        Os.append(place(Ns[i], CAs[i], Cs[i], 1.231, 120.8, psi + 180.0))
+        if i + 1 < n:
+            Ns.append(place(Ns[i], CAs[i], Cs[i], 1.329, 116.2, psi))
+            CAs.append(place(CAs[i], Cs[i], Ns[i + 1], 1.458, 121.7, 180.0))
+            Cs.append(place(Cs[i], Ns[i + 1], CAs[i + 1], 1.525, 111.0, phi))
+    return np.stack([np.stack([Ns[i], CAs[i], Cs[i], Os[i]]) for i in range(n)]).reshape(-1, 3).astype(np.float32)
+
+
+def plain_table(n):
+    return np.arange(4 * n, dtype=np.int32).reshape(n, 4)
+
+
+def records(raw):
+    """{(chain, resSeq): 'H' / 'E'} of the HELIX and SHEET records of a PDB file"""
+    out = {}
+    for line in raw.decode(errors="replace").splitlines():
+        try:
+            if line.startswith("HELIX "):
+                c, a, b, s = line[19], int(line[21:25]), int(line[33:37]), "H"
+            elif line.startswith("SHEET "):
+                c, a, b, s = line[21], int(line[22:26]), int(line[33:37]), "E"
+            else:
+                continue
+        except ValueError:
+            continue
+        for r in range(a, b + 1):
+            out[(c, r)] = s
+    return out
+
+
+def main():
+    from pesto_amd.structure_io import Structure
+    out, flagged = {}, {}
+
+    def run(name, X, table, pro, chain, sizes, scale=1.0, allow=()):
+        """the restatement over a ragged batch and all frames: codes [F, R], partners / energies [F, R, 4]"""
+        X = np.asarray(X, np.float32)
+        X = X[None] if X.ndim == 2 else X
+        cs, ps, es, fl = [], [], [], []
+        for f in range(X.shape[0]):
+            c1, p1, e1, start = [], [], [], 0
+            for n in sizes:
+                c, p, e = dssp(X[f], table[start:start + n].tolist(), pro[start:start + n].tolist(), chain[start:start + n].tolist(), scale, fl)
+                c1.append(c); p1.append(p); e1.append(e)
+                start += n
+            cs.append(np.concatenate(c1)); ps.append(np.concatenate(p1)); es.append(np.concatenate(e1))
+        fl = [x for x in fl if x[0] not in allow]
+        flagged[name] = fl
+        return np.stack(cs), np.stack(ps), np.stack(es)
+
+    def store(name, X, table, pro, chain, sizes=None, allow=(), must_be_clean=True):
+        X = np.asarray(X, np.float32)
+        X = X[None] if X.ndim == 2 else X
+        table, pro, chain = np.asarray(table, np.int32).reshape(-1, 4), np.asarray(pro, np.uint8), np.asarray(chain, np.int32)
+        sizes = [len(table)] if sizes is None else list(sizes)
+        c, p, e = run(name, X, table, pro, chain, sizes, allow=allow)
+        assert not (must_be_clean and flagged[name]), (name, flagged[name][:5])
+        out[f"{name}_X"], out[f"{name}_table"], out[f"{name}_pro"], out[f"{name}_chain"] = X, table, pro, chain
+        out[f"{name}_sizes"], out[f"{name}_codes"], out[f"{name}_partners"], out[f"{name}_em"] = np.array(sizes, np.int32), c, p, e
+        return c
+
+    # ---- batch
+    parts, agreement = [], {}
+    for name in BATCH:
+        raw = gzip.open(os.path.join(OUT, "pdb", name + ".gz"), "rb").read()
+        d = Structure.parse_pdb(raw).to_dict()
+        table, pro, chain, keys = residue_table(d)
+        out[f"batch_full_{name[:4]}_table"], out[f"batch_full_{name[:4]}_pro"], out[f"batch_full_{name[:4]}_chain"] = table, pro, chain
+        keep = np.nonzero((table >= 0).any(1))[0]
+        parts.append(compact(d["xyz"], table, pro, chain, keep) + ([keys[r] for r in keep], records(raw), name))
+    sizes = [len(p[1]) for p in parts]
+    Xb = np.concatenate([p[0] for p in parts])
+    shift = np.cumsum([0] + [p[0].shape[0] for p in parts])
+    tb = np.concatenate([np.where(p[1] >= 0, p[1] + s, -1) for p, s in zip(parts, shift)]).astype(np.int32)
+    codes = store("batch", Xb, tb, np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts]), sizes)[0]
+    out["batch_names"] = np.array(BATCH)
+    cuts = np.cumsum([0] + sizes)
+    per = {p[6]: codes[cuts[k]:cuts[k + 1]] for k, p in enumerate(parts)}
+    simple = np.array(["C", "H", "E", "E", "H", "H", "C", "C", "NA"])
+    for k, p in enumerate(parts):
+        c, keys, rec = per[p[6]], p[4], p[5]
+        mine = simple[c]
+        theirs = np.array([{"H": "H", "E": "E"}.get(rec.get((ck[0][:1], ck[1])), "C") for ck in keys])
+        okr = mine != "NA"
+        agree = float((mine[okr] == theirs[okr]).mean())
+        sh = okr & (theirs == "E")
+        sheet_e = float((mine[sh] == "E").mean()) if sh.any() else float("nan")
+        agreement[p[6]] = (agree, sheet_e)
+        print(f"{p[6]}: {len(c)} residues, {int((~okr).sum())} NA, agreement with HELIX/SHEET {agree:.3f}, SHEET residues E {sheet_e:.3f}")
+        print("   ", text(c)[:160])
+    out["agreement_names"] = np.array(list(agreement))
+    out["agreement_simplified"] = np.array([v[0] for v in agreement.values()])
+    out["agreement_sheet_is_E"] = np.array([v[1] for v in agreement.values()])
+
+    # ---- scale = 10 on float32(X / 10): the structures that stay unflagged and keep their codes
+    X10 = (Xb / np.float32(10.0)).astype(np.float32)
+    ok10 = []
+    for k, p in enumerate(parts):
+        sl = slice(cuts[k], cuts[k + 1])
+        fl = []
+        t_loc = np.where(tb[sl] >= 0, tb[sl] - shift[k], -1)
+        c10 = dssp(X10[shift[k]:shift[k + 1]], t_loc.tolist(), out["batch_pro"][sl].tolist(), out["batch_chain"][sl].tolist(), 10.0, fl)[0]
+        if not fl and np.array_equal(c10, codes[sl]):
+            ok10.append(k)
+    assert ok10, "no structure survives the rounding of X / 10 unflagged"
+    out["scale10_X"], out["scale10_ok"] = X10, np.array(ok10, np.int32)
+    print("scale10: structures", [BATCH[k] for k in ok10])
+
+    # ---- frames
+    rng = np.random.default_rng(1983)
+    X0, t0 = parts[0][0].astype(np.float64), parts[0][1]
+    frames = []
+    for f in range(8):
+        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+        q = q * np.sign(np.linalg.det(q))
+        frames.append(((X0 - X0.mean(0)) @ q + rng.normal(size=3) * 20.0 + rng.normal(size=X0.shape) * 0.3).astype(np.float32))
+    cf = store("frames", np.stack(frames), t0, parts[0][2], parts[0][3])
+    print("frames: residues whose code differs from frame 0:", [(int((cf[f] != cf[0]).sum())) for f in range(8)])
+
+    # ---- planted
+    names = []
+
+    def plant(name, X, table, pro=None, chain=None, sizes=None, allow=()):
+        n = len(table)
+        names.append(name)
+        return store("planted_" + name, X, table, np.zeros(n, np.uint8) if pro is None else pro, np.zeros(n, np.int32) if chain is None else chain,
+                     sizes, allow)[0]
+    helix = ideal(12, -57.0, -47.0)
+    c = plant("helix", helix, plain_table(12))
+    assert text(c) == " " + "H" * 10 + " ", text(c)
+    e = out["planted_helix_em"][0]
+    print("helix:", repr(text(c)), "e(i+4 -> i) =", e[4:, 0].tolist())
+    c = plant("helix310", ideal(12, -49.0, -26.0), plain_table(12))
+    print("3-10 :", repr(text(c)))
+    assert "GGG" in text(c)
+    pro = np.zeros(12, np.uint8); pro[6] = 1
+    c = plant("helix_proline", helix, plain_table(12), pro=pro)
+    print("pro  :", repr(text(c)))
+    # a proline donates nothing; one missing i+4 -> i bond leaves every residue of the helix inside two consecutive turns
+    assert out["planted_helix_proline_partners"][0][6, :2].tolist() == [-1, -1] and text(c) == " " + "H" * 10 + " "
+    cn = helix[4 * 6].astype(np.float64) - helix[4 * 5 + 2].astype(np.float64)
+    Xs = helix.copy(); Xs[4 * 6:] += (cn / np.linalg.norm(cn) * 2.0).astype(np.float32)       # C 5 - N 6: 1.33 + 2.0 A
+    c = plant("helix_stretched", Xs, plain_table(12))
+    assert dist(Xs[4 * 5 + 2].astype(float), Xs[4 * 6].astype(float)) > 2.6
+    print("cut  :", repr(text(c)))
+    tm = plain_table(12); tm[5, 3] = -1
+    c = plant("helix_missing_O", helix, tm)
+    assert c[5] == NA and (c != NA).sum() == 11
+    print("noO  :", repr(text(c)))
+    Xn = helix.copy(); Xn[4 * 4 + 1, 1] = np.nan
+    c = plant("helix_nan", Xn, plain_table(12))
+    print("nan  :", repr(text(c)))
+    for n in (1, 2, 4, 5, 6):
+        c = plant(f"helix_R{n}", helix[:4 * n], plain_table(n))
+        print(f"R={n}  :", repr(text(c)))
+        assert n > 5 or not (c == H).any()
+    c = plant("one_between", np.concatenate([helix, helix[:4] + np.float32(3.0), helix]), plain_table(25), sizes=[12, 1, 12])
+    assert text(c) == " " + "H" * 10 + " " + " " + " " + "H" * 10 + " "
+    for ca, tag in ((9.0, "ca_9_0"), (8.5, "ca_8_5")):
+        # residue 1 donates (its H from C, O of residue 0), residue 2 (another chain) accepts; CA 1 - CA 2 lies on the x axis
+        Xp = np.array([[-3.0, 3.0, 0.0], [-1.8, 2.8, 0.0], [0.6, 1.95, 0.0], [-0.63, 1.95, 0.0],
+                       [1.2, 0.8, 0.0], [0.0, 0.0, 0.0], [-0.8, -1.2, 0.0], [-0.8, -2.4, 0.0],
+                       [ca + 0.5, 1.3, 0.0], [ca, 0.0, 0.0], [5.3, 0.8, 0.0], [4.1, 0.8, 0.0]], np.float32)
+        c = plant(tag, Xp, plain_table(3), chain=np.array([0, 0, 1], np.int32), allow=("ca",) if ca == 9.0 else ())
+        p, e = out[f"planted_{tag}_partners"][0], out[f"planted_{tag}_em"][0]
+        print(tag, p[1].tolist(), e[1].tolist())
+        assert (p[1, 0] == 2 and e[1, 0] < -500) if ca == 8.5 else (2 not in p[1, :2].tolist())
+    # crops of the batch
+    def crop(src, rows):
+        p = parts[src]
+        return compact(p[0], p[1], p[2], p[3], np.array(rows))
+
+    def ladders_of(src):
+        c = per[parts[src][6]]
+        P = out["batch_partners"][0][cuts[src]:cuts[src + 1]]
+        return c, P
+    c1, _ = ladders_of(2)                                       # 1OL5
+    s = text(c1)
+    want = "EEEEEEEEEETTEEEEEEEETTT  EEEEEEEE"
+    at = s.find(want)
+    assert at >= 0, "the 1OL5 meander is not where the definition puts it:\n" + s
+    hair = list(range(at - 2, at + 22))
+    mea = list(range(at - 2, at + len(want) + 2))
+    c = plant("hairpin_1OL5", *crop(2, hair))
+    print("hairpin:", repr(text(c)))
+    assert text(c)[2:22] == want[:20]
+    c = plant("meander_1OL5", *crop(2, mea))
+    print("meander:", repr(text(c)))
+    # (the end of the third strand pairs with a strand outside the crop)
+    assert text(c)[2:2 + 25] == want[:25] and E not in c[2 + 20:2 + 25].tolist() and text(c)[2 + 25:2 + 29] == "EEEE"
+    # an antiparallel and a parallel pair: the first ladder of each kind with four bridges or more, two residues of margin
+    found = {}
+    for src in range(len(parts)):
+        n = sizes[src]
+        sl = slice(cuts[src], cuts[src + 1])
+        tl = np.where(tb[sl] >= 0, tb[sl] - shift[src], -1)
+        _, P, Em = dssp(Xb[shift[src]:shift[src + 1]], tl.tolist(), out["batch_pro"][sl].tolist(), out["batch_chain"][sl].tolist())
+
+        def bd(d, a):
+            return 0 <= d < n and 0 <= a < n and any(P[d, k] == a and Em[d, k] < -500 for k in range(2))
+        for i in range(1, n - 1):
+            for j in range(i + 6, n - 1):
+                for kind, step in (("parallel", 1), ("antiparallel", -1)):
+                    if kind in found:
+                        continue
+                    run_ok = True
+                    need = 4 if kind == "antiparallel" else 2          # (the five files hold no longer parallel ladder)
+                    for m in range(need):
+                        a, b = i + m, j + step * m
+                        if not (0 < b < n - 1) or abs(b - a) < 6:
+                            run_ok = False
+                            break
+                        if kind == "parallel":
+                            hit = (bd(a + 1, b) and bd(b, a - 1)) or (bd(b + 1, a) and bd(a, b - 1))
+                        else:
+                            hit = (bd(a + 1, b - 1) and bd(b + 1, a - 1)) or (bd(b, a) and bd(a, b))
+                        run_ok = run_ok and hit
+                        if not run_ok:
+                            break
+                    if run_ok:
+                        lo, hi = sorted((j, j + step * (need - 1)))
+                        rows = sorted(set(range(max(0, i - 2), i + need + 2)) | set(range(max(0, lo - 2), min(n, hi + 3))))
+                        found[kind] = (src, rows)
+        if len(found) == 2:
+            break
+    for kind in ("antiparallel", "parallel"):
+        assert kind in found, kind
+        src, rows = found[kind]
+        c = plant("pair_" + kind, *crop(src, rows))
+        print(kind, BATCH[src], rows[0], rows[-1], repr(text(c)))
+        assert (c == E).sum() >= (6 if kind == "antiparallel" else 4)
+    # tile and workgroup edges: 6O1T cut to 127 .. 129 and 255 .. 257 residues
+    assert sizes[3] >= 257
+    for n in (127, 128, 129, 255, 256, 257):
+        plant(f"crop6O1T_{n}", *crop(3, list(range(n))))
+    out["planted_names"] = np.array(names)
+    assert not any(flagged.values())
+    path = os.path.join(OUT, "dssp.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
+    print("agreement:", {k: (round(v[0], 3), round(v[1], 3)) for k, v in agreement.items()})
+
+
+if __name__ == "__main__":
+    main()
