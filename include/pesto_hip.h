@@ -446,6 +446,76 @@ int pesto_superpose(pesto_model* m, int64_t F, int64_t F_ref, int64_t N_ref, int
 int pesto_residue_centroids(pesto_model* m, int64_t F, int64_t N, int64_t R, const float* X_frames, const int32_t* perm, const int32_t* off,
                             float* out, int32_t ptr_kind, void* stream);
 
+/* ---- docking metrics and frame contacts (the remaining array functions of md_analysis/mdtraj_utils/trajectory_utils.py) ----
+ * Failures of the entry points below are reported through pesto_docking_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the trajectory group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ * Coordinates are float32 [F,N,3]. The distance is the trajectory group's float32 one times a scale, r_thr and scale being float32:
+ *     d = fl32(sqrt_rn((dx*dx + dy*dy) + dz*dz)) * scale, every operation rounded as written, the root correctly rounded;
+ * r_thr finite, scale positive and finite. Every output is bit-identical from call to call. */
+const char* pesto_docking_last_error(void);
+
+enum {
+    PESTO_DOCKING_MAX_FRAMES = 1 << 23,       /* a workgroup of 256 threads per frame, below 2^32 threads per launch */
+    PESTO_DOCKING_MAX_MAP_WORDS = 1 << 28     /* F * ceil(Ra * Rb / 32) of pesto_frame_residue_contacts: two int32 of scratch per word */
+};
+
+/* replaces: the frame loop of contacts (trajectory_utils.py:408-423; per frame a dense [Na,Nb] torch matrix, torch.where and three
+ * copies to the host). xyz_a [F,Na,3], xyz_b [F,Nb,3], Na * Nb < 2^31. Frame f owns the rows offsets_out[f] .. offsets_out[f+1] of
+ *     pairs_out int32 [cap_pairs,2]: exactly the (i, j) with d < r_thr, i ascending, then j ascending (torch.where's order); a NaN
+ *                distance is in no list
+ *     d_out float32 [cap_pairs]: their d
+ *     offsets_out int64 [F+1]; sizes_out int64 [1] (HOST): K, the number of contacts of all frames
+ * The outputs are complete when K <= cap_pairs (1 <= cap_pairs < 2^30); otherwise only offsets_out and K are, and the call must be
+ * repeated with a larger capacity (the count is the one synchronisation of a call). A tiled brute-force search, count -> scan -> emit;
+ * the [Na,Nb] matrix is never stored. */
+int pesto_frame_contacts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, const float* xyz_a, const float* xyz_b, float r_thr, float scale,
+                         int64_t cap_pairs, int64_t* offsets_out, int32_t* pairs_out, float* d_out, int64_t* sizes_out, int32_t ptr_kind,
+                         void* stream);
+
+/* replaces: atoms_to_residue_contacts (trajectory_utils.py:233-264; np.unique and a Python loop per frame and residue pair). offsets int64
+ * [F+1], pairs int32 [K,2], d float32 [K]: the lists of pesto_frame_contacts (0 <= K < 2^30; d non-negative, no NaN). res_a int32 [Na],
+ * res_b int32 [Nb]: the residue row of each atom, in [0, Ra) and [0, Rb). Frame f owns the rows roffsets_out[f] .. roffsets_out[f+1] of
+ *     rpairs_out int32 [cap_rpairs,2]: the distinct (res_a[i], res_b[j]) of the frame's contacts in lexicographic order (np.unique, axis 0)
+ *     dmin_out float32 [cap_rpairs]: the smallest d among the contacts of each
+ *     roffsets_out int64 [F+1]; sizes_out int64 [1] (HOST): U, the number of residue pairs of all frames
+ * with the capacity protocol of pesto_frame_contacts (1 <= cap_rpairs < 2^30). A bit map of [Ra,Rb] per frame (at most
+ * PESTO_DOCKING_MAX_MAP_WORDS words in all), its set bits emitted in index order, the minimum by an integer atomic on the bits of d: exact
+ * and independent of the order of the threads. An atom index or residue row outside its range makes the call return PESTO_ERR_INVALID. */
+int pesto_frame_residue_contacts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, int64_t K, const int64_t* offsets, const int32_t* pairs,
+                                 const float* d, const int32_t* res_a, const int32_t* res_b, int32_t Ra, int32_t Rb, int64_t cap_rpairs,
+                                 int64_t* roffsets_out, int32_t* rpairs_out, float* dmin_out, int64_t* sizes_out, int32_t ptr_kind, void* stream);
+
+/* replaces: interface_residues_within (trajectory_utils.py:267-297; a dense distance matrix and an [N,residues] isclose matrix). xyz0
+ * [N,3]: the reference frame; ids_a int32 [na], ids_b int32 [nb]: the atoms of the two subunits; res_of_atom int32 [N] in [0, R).
+ * flags_out uint8 [2,N]: flags_out[0][n] = 1 where the residue of atom n holds an atom of ids_a with d <= r_thr to some atom of ids_b,
+ * flags_out[1][n] likewise for ids_b against ids_a (every atom of such a residue, in ids_a or not; note <=, where the contacts have <).
+ * An index or row outside its range makes the call return PESTO_ERR_INVALID. */
+int pesto_interface_atoms(pesto_model* m, int64_t N, const float* xyz0, int64_t na, const int32_t* ids_a, int64_t nb, const int32_t* ids_b,
+                          const int32_t* res_of_atom, int32_t R, float r_thr, float scale, uint8_t* flags_out, int32_t ptr_kind, void* stream);
+
+/* replaces: interface_rigid_docking (trajectory_utils.py:474-499; two batched SVD superpositions, a transformed copy of the whole
+ * trajectory between them, scipy's as_rotvec). xyz_ref [F_ref,N,3], F_ref = 1 or F; xyz [F,N,3]; sel_R int32 [n_R], sel_L int32 [n_L]:
+ * the receptor's and the ligand's interface atoms (in [0, N), else PESTO_ERR_INVALID; at least 3 each). Per frame, in double from the float32
+ * inputs: the fit of pesto_superpose on sel_R; the atoms of sel_L alone transformed by it; their fit onto the reference's sel_L, giving
+ * t_cm, R2, t_ref2 (the same sums, order and rotation, degenerate selections included).
+ *     t_out float32 [F,3] = t_ref2 - t_cm, in the coordinates' unit
+ *     r_out float32 [F,3] = the rotation vector of R2 as scipy's Rotation.from_matrix(R2).as_rotvec() reads it: unit quaternion with
+ *           w >= 0, angle = 2 atan2(|v|, w) in [0, pi], r = angle v / |v|, 0 for the identity. Near angle = pi the sign of the axis is
+ *           decided by rounding, here as anywhere.
+ * A selection that equals the reference's bit for bit is fitted by the identity itself (no rotation within rounding of it): a frame that
+ * is the reference gives t = 0 and r = 0 exactly. One kernel, one workgroup per frame; no [F,N,3] intermediate. */
+int pesto_rigid_docking(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_R,
+                        const int32_t* sel_R, int64_t n_L, const int32_t* sel_L, float* t_out, float* r_out, int32_t ptr_kind, void* stream);
+
+/* replaces: irmsd (trajectory_utils.py:328-338; interface selection, SVD superposition of copies of the trajectory, the rmsd expression)
+ * once the interface's CA atoms are known: sel int32 [n_sel], n_sel >= 3, in [0, N) (else PESTO_ERR_INVALID), the same atoms of xyz_ref
+ * [F_ref,N,3] and xyz [F,N,3]. rmsd_out float32 [F]: the rmsd_out of pesto_superpose fitted on sel on both sides, bit for bit (the same
+ * kernel as pesto_rigid_docking, stopped after its first fit) - except that a selection equal to the reference's bit for bit is fitted by
+ * the identity itself and gives exactly 0, where pesto_superpose leaves the rounding residue of its rotation (some 1e-15). */
+int pesto_interface_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_sel,
+                         const int32_t* sel, double scale, float* rmsd_out, int32_t ptr_kind, void* stream);
+
 /* ---- solvent-accessible surface area (the reference's two uses of md.shrake_rupley) ----
  * replaces: wrapper_solvent_accessible_surface_area (interfaceome/solvent_accessible_surface_area.py:27-31, one structure at a time in a
  * two-process pool) and sasa (md_analysis/mdtraj_utils/trajectory_utils.py:428-438, a Python loop over the frames).

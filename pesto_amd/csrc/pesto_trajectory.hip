@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "pesto_call.h"
+#include "pesto_geom.h"
 
 namespace pesto {
 
@@ -31,13 +32,6 @@ constexpr int LPAD = LF + 1;
 constexpr int64_t LOGLIK_SCRATCH = 64 << 20;   // bytes of tile partials per pass of pesto_contact_loglik
 constexpr int JU = 4;               // ... with JU partner atoms' bin searches side by side
 
-// NumPy's float32 squared distance, no contraction: (dx*dx + dy*dy) + dz*dz
-__device__ __forceinline__ float dist2(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
 // Bin search over thr[0 .. 2 * top): the B + 1 thresholds, then +inf up to twice `top`, the largest power of two <= B. Starting from
 // lo = 0, the steps top, top / 2, ... 1 leave the largest index whose threshold is <= s (given thr[0] <= s): the same number of steps for
 // every lane, no branch. An empty bin (thr[b] == thr[b+1]) is never chosen; s >= thr[B] ends at B or above, which is no bin.
@@ -47,19 +41,6 @@ __device__ __forceinline__ void search_step(const float* thr, int step, float s,
 }
 
 __device__ __forceinline__ void lds_count(unsigned* p) { (void)__hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// sum of v over the workgroup, the same bits in every thread: butterfly within each wave, then the four waves in turn.
-// red: NT / 64 doubles of LDS; two barriers
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) t += red[w];
-    return t;
-}
 
 // ---- statistical contacts model
 // replaces: contacts_distribution's frame loop (md_analysis/mdtraj_utils/statistical_contacts_model.py:7-30). One thread per atom pair
@@ -281,69 +262,7 @@ __global__ __launch_bounds__(NT) void k_sum_i64(int n, const long long* __restri
     if (threadIdx.x == 0) out[0] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// ---- superposition
-// R of the 3x3 covariance H = (ref - t_ref)^T (xyz - t) = U S V^T: R = V diag(1, 1, det(U) det(V)) U^T, by one-sided Jacobi in double
-// (columns of H V rotated until orthogonal: H V = U S). With U2' = U0 x U1 and the true U2 = +-U2', the sign cancels against det(U):
-// R = V0 U0^T + V1 U1^T + det(V) V2 U2'^T, columns ordered by singular value, so the smallest one is never divided by.
-__device__ void kabsch_rotation(const double* H, double* R) {
-    double A[3][3], V[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) { A[a][b] = H[3 * a + b]; V[a][b] = a == b ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double alpha = 0.0, beta = 0.0, gamma = 0.0;
-                for (int k = 0; k < 3; ++k) { alpha += A[k][p] * A[k][p]; beta += A[k][q] * A[k][q]; gamma += A[k][p] * A[k][q]; }
-                if (fabs(gamma) <= 1e-15 * sqrt(alpha * beta)) continue;     // orthogonal to a few units of double rounding (also gamma == 0)
-                rotated = true;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-                for (int k = 0; k < 3; ++k) {
-                    const double ap = A[k][p], aq = A[k][q], vp = V[k][p], vq = V[k][q];
-                    A[k][p] = c * ap - s * aq; A[k][q] = s * ap + c * aq;
-                    V[k][p] = c * vp - s * vq; V[k][q] = s * vp + c * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    double n[3];
-    for (int k = 0; k < 3; ++k) n[k] = sqrt(A[0][k] * A[0][k] + A[1][k] * A[1][k] + A[2][k] * A[2][k]);
-    int i0 = 0, i1 = 1, i2 = 2;
-    if (n[i0] < n[i1]) { const int t = i0; i0 = i1; i1 = t; }
-    if (n[i1] < n[i2]) { const int t = i1; i1 = i2; i2 = t; }
-    if (n[i0] < n[i1]) { const int t = i0; i0 = i1; i1 = t; }
-    // A degenerate selection leaves the rotation about its line (rank 1: collinear atoms) or altogether (rank 0) undetermined. Like an SVD
-    // library, return SOME proper rotation then, never a division by zero: a missing left vector is any unit vector orthogonal to the ones
-    // there are (the least-squares fit is the same for every such choice).
-    double U0[3] = {1.0, 0.0, 0.0}, U1[3], U2[3];
-    const double tiny = 1e-300;
-    if (n[i0] > tiny)
-        for (int k = 0; k < 3; ++k) U0[k] = A[k][i0] / n[i0];
-    if (n[i1] > tiny && n[i1] > 1e-14 * n[i0]) {
-        double dot = 0.0, len = 0.0;
-        for (int k = 0; k < 3; ++k) { U1[k] = A[k][i1] / n[i1]; dot += U1[k] * U0[k]; }
-        for (int k = 0; k < 3; ++k) { U1[k] -= dot * U0[k]; len += U1[k] * U1[k]; }        // (re-orthogonalised: a no-op away from degeneracy)
-        len = sqrt(len);
-        for (int k = 0; k < 3; ++k) U1[k] /= len;
-    } else {
-        const int c = fabs(U0[0]) <= fabs(U0[1]) && fabs(U0[0]) <= fabs(U0[2]) ? 0 : fabs(U0[1]) <= fabs(U0[2]) ? 1 : 2;    // the axis least along U0
-        double e[3] = {0.0, 0.0, 0.0}, len = 0.0;
-        e[c] = 1.0;
-        for (int k = 0; k < 3; ++k) { U1[k] = e[k] - U0[c] * U0[k]; len += U1[k] * U1[k]; }
-        len = sqrt(len);
-        for (int k = 0; k < 3; ++k) U1[k] /= len;
-    }
-    U2[0] = U0[1] * U1[2] - U0[2] * U1[1];
-    U2[1] = U0[2] * U1[0] - U0[0] * U1[2];
-    U2[2] = U0[0] * U1[1] - U0[1] * U1[0];
-    const double detV = V[0][i0] * (V[1][i1] * V[2][i2] - V[2][i1] * V[1][i2]) - V[0][i1] * (V[1][i0] * V[2][i2] - V[2][i0] * V[1][i2]) +
-                        V[0][i2] * (V[1][i0] * V[2][i1] - V[2][i0] * V[1][i1]);
-    for (int a = 0; a < 3; ++a)
-        for (int c = 0; c < 3; ++c) R[3 * a + c] = V[a][i0] * U0[c] + V[a][i1] * U1[c] + detV * V[a][i2] * U2[c];
-}
-
+// ---- superposition (the rotation of a covariance: kabsch_rotation of pesto_geom.h)
 // replaces: superpose_transform and the rmsd expression (trajectory_utils.py:190-207, 308-325). One workgroup per frame over the n_sel
 // selected atoms: means, covariance, rotation, then the deviation of the transformed selection from the reference's. tr [F][15] keeps
 // t, R, t_ref in double for k_superpose_apply.
@@ -362,7 +281,7 @@ __global__ __launch_bounds__(NT) void k_superpose_fit(int Fr, int Nr, int N, int
         const float* y = Y + (size_t)(sel_ref ? sel_ref[k] : k) * 3;
         for (int c = 0; c < 3; ++c) { m[c] += (double)x[c]; m[3 + c] += (double)y[c]; }
     }
-    for (int c = 0; c < 6; ++c) m[c] = block_sum(m[c], red) / (double)n_sel;
+    for (int c = 0; c < 6; ++c) m[c] = block_sum<NT>(m[c], red) / (double)n_sel;
     double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int k = threadIdx.x; k < n_sel; k += NT) {
         const float* x = X + (size_t)(sel ? sel[k] : k) * 3;
@@ -370,7 +289,7 @@ __global__ __launch_bounds__(NT) void k_superpose_fit(int Fr, int Nr, int N, int
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) H[3 * a + b] += ((double)y[a] - m[3 + a]) * ((double)x[b] - m[b]);
     }
-    for (int c = 0; c < 9; ++c) H[c] = block_sum(H[c], red);
+    for (int c = 0; c < 9; ++c) H[c] = block_sum<NT>(H[c], red);
     if (threadIdx.x == 0) {
         double R[9];
         kabsch_rotation(H, R);
@@ -392,7 +311,7 @@ __global__ __launch_bounds__(NT) void k_superpose_fit(int Fr, int Nr, int N, int
             dev += e * e;
         }
     }
-    dev = block_sum(dev, red);
+    dev = block_sum<NT>(dev, red);
     if (threadIdx.x == 0) rmsd[f] = (float)(sqrt(dev / (double)n_sel) * scale);
 }
 
@@ -423,23 +342,6 @@ __global__ __launch_bounds__(NT) void k_residue_centroids(size_t total, int N, i
 }
 
 // ---- host side
-float from_bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-
-// smallest non-negative float s (+inf if none) for which pred(s) holds; pred must be monotonic (false ... false true ... true) over
-// 0 .. +inf, whose bit patterns are ordered like the values
-template <class Pred> float first_true(Pred pred) {
-    uint32_t lo = 0u, hi = 0x7f800000u;     // +0 .. +inf
-    if (pred(from_bits(lo))) return 0.f;
-    if (!pred(from_bits(hi))) return INFINITY;
-    while (hi - lo > 1u) {                  // pred(lo) false, pred(hi) true
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (pred(from_bits(mid))) hi = mid; else lo = mid;
-    }
-    return from_bits(hi);
-}
-
-float sqrt_rn(float s) { volatile float r = std::sqrt(s); return r; }
-
 int pow2_floor(int B) { int t = 1; while (2 * t <= B) t *= 2; return t; }
 
 // the squared-distance thresholds of the bin edges: d >= edge  <=>  s >= sq, for every float32 s = d * d summed as dist2 does.
