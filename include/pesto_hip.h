@@ -516,6 +516,63 @@ int pesto_rigid_docking(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, con
 int pesto_interface_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_sel,
                          const int32_t* sel, double scale, float* rmsd_out, int32_t ptr_kind, void* stream);
 
+/* ---- hydrogen bonds and periodic unwrapping (hydrogen_bonds and unwrap_pbc of md_analysis/mdtraj_utils/trajectory_utils.py) ----
+ * Failures of the entry points below are reported through pesto_hbonds_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ *
+ * Definition (md.baker_hubbard's documented criterion in this library's arithmetic). xyz float32 [F,N,3]; dh int32 [P,2], rows (donor
+ * atom, hydrogen atom); acc int32 [A], the acceptor atoms; every index in [0, N), else PESTO_ERR_INVALID (checked on the device). The
+ * candidates are the triplets (dh[p,0], dh[p,1], acc[a]) with acc[a] != dh[p,0], in the order p ascending, then a ascending. With H, D, A
+ * the float32 coordinates of a triplet in a frame:
+ *     d  = fl32(sqrt_rn((dx*dx + dy*dy) + dz*dz)) * scale between H and A, as in the docking group, and d < r_thr (r_thr, scale: float32,
+ *          positive and finite)
+ *     u = D - H, v = A - H, c = (ux*vx + uy*vy) + uz*vz, uu and vv likewise, in double, every operation rounded as written, and
+ *          c < 0 && c*c > cos2_angle * (uu*vv)      cos2_angle = cos(angle)^2 in [0, 1) for a D-H-A angle threshold in [90, 180) degrees
+ * make the triplet bonded in that frame; a NaN, uu = 0 or vv = 0 does not. Every output is bit-identical from call to call. */
+const char* pesto_hbonds_last_error(void);
+
+enum {
+    PESTO_HBONDS_MAX_FRAMES = 1 << 23,        /* a workgroup per frame and donor tile, below 2^32 threads per launch */
+    PESTO_HBONDS_MAX_PAIRS = 0x7fffffff,      /* P * A, the candidates of one frame */
+    PESTO_HBONDS_MAX_LIST = (1 << 30) - 1,    /* entries of one list */
+    PESTO_HBONDS_DONOR_TILE = 32              /* donor pairs of one workgroup */
+};
+
+/* replaces: the frame loop of hydrogen_bonds (trajectory_utils.py:441-471; md.baker_hubbard restarted for every frame, then np.isin
+ * filters in Python). P * A <= PESTO_HBONDS_MAX_PAIRS and F * ceil(P / 32) < 2^24. Frame f owns the rows offsets_out[f] .. offsets_out[f+1] of
+ *     triplets_out int32 [cap,3]: the bonded (donor, hydrogen, acceptor) atoms of the frame in candidate order
+ *     d_out float32 [cap]: their d
+ *     offsets_out int64 [F+1]; sizes_out int64 [1] (HOST): K, the number of bonds of all frames
+ * with the capacity protocol of pesto_frame_contacts (1 <= cap < 2^30): complete when K <= cap, otherwise only offsets_out and K are and
+ * nothing beyond cap is written. group int8 [N] or NULL: when given, only triplets whose donor and acceptor atoms carry different
+ * non-zero groups are listed (0: in neither subunit). A tiled brute-force search, count -> scan -> emit; no [P,A] array is stored. */
+int pesto_frame_hbonds(pesto_model* m, int64_t F, int64_t N, int64_t P, int64_t A, const float* xyz, const int32_t* dh, const int32_t* acc,
+                       const int8_t* group, float r_thr, float scale, double cos2_angle, int64_t cap, int64_t* offsets_out, int32_t* triplets_out,
+                       float* d_out, int64_t* sizes_out, int32_t ptr_kind, void* stream);
+
+/* replaces: md.baker_hubbard over a whole trajectory, which hydrogen_bonds (trajectory_utils.py:441-471) restarts for every frame. n[p,a]
+ * is the number of frames in which candidate (p, a) is bonded; it is listed iff (double)n / (double)F > freq (strict; freq finite, >= 0).
+ *     triplets_out int32 [cap,3]: the listed triplets in candidate order;   counts_out int32 [cap]: their n
+ *     sizes_out int64 [1] (HOST): k, their number
+ * with the same capacity protocol. A workgroup owns 32 donor pairs x 64 acceptors and loops over the frames with the counts in registers;
+ * the scratch is one int32 per (donor pair, 64 acceptors). */
+int pesto_hbond_occupancy(pesto_model* m, int64_t F, int64_t N, int64_t P, int64_t A, const float* xyz, const int32_t* dh, const int32_t* acc,
+                          float r_thr, float scale, double cos2_angle, double freq, int64_t cap, int32_t* triplets_out, int32_t* counts_out,
+                          int64_t* sizes_out, int32_t ptr_kind, void* stream);
+
+/* replaces: unwrap_pbc (trajectory_utils.py:28-64; a Python loop over chains and their 27 periodic images, a copy of the trajectory).
+ * xyz [F,N,3]; unitcell_lengths float32 [F,3]; perm int32 [N]: the atoms ordered by molecule (in [0, N), else PESTO_ERR_INVALID);
+ * mol_off int32 [M+1] (HOST): molecule m holds perm[mol_off[m] .. mol_off[m+1]), none empty; masses float64 [N]. In double:
+ *     com[f,m] = sum(mass x) / sum(mass) over the molecule, in a fixed order
+ *     for m >= 1, image k = 0 .. 26 is dV[k] = (g[(k/3)%3], g[k/9], g[k%3]), g = (0, 1, -1): y slowest, then x, then z
+ *     dist[k] = sqrt((tx*tx + ty*ty) + tz*tz), t = (com[f,m] + L[f] * dV[k]) - com[f,0], every operation rounded as written
+ *     image_out int32 [F,M] = the first k of minimum dist (0 for molecule 0)
+ *     xyz_out float32 [F,N,3] = fl32((double)x + (double)L[f,c] * dV[k][c]) for every atom of m; molecule 0 is copied
+ * A NaN in com[f,m], com[f,0] or L[f] gives k = 0 and a copy of that molecule's frame. xyz is never modified. */
+int pesto_unwrap_pbc(pesto_model* m, int64_t F, int64_t N, int64_t M, const float* xyz, const float* unitcell_lengths, const int32_t* perm,
+                     const int32_t* mol_off, const double* masses, float* xyz_out, int32_t* image_out, int32_t ptr_kind, void* stream);
+
 /* ---- solvent-accessible surface area (the reference's two uses of md.shrake_rupley) ----
  * replaces: wrapper_solvent_accessible_surface_area (interfaceome/solvent_accessible_surface_area.py:27-31, one structure at a time in a
  * two-process pool) and sasa (md_analysis/mdtraj_utils/trajectory_utils.py:428-438, a Python loop over the frames).

@@ -8,7 +8,8 @@ from .config import CONFIGS, config_i_v3_0, config_i_v3_1, config_i_v4_0, config
 __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_assemblies", "patches", "interface_patches",
            "interface_patches_batch", "residue_ca", "save_patches", "trajectory", "StatisticalContactsModel", "contacts_distribution", "contact_counts",
            "div_KL", "interface_ensemble_comparison", "residue_contact_maps", "native_contacts", "fnat", "superpose_transform", "superpose", "rmsd",
-           "residue_centroids", "docking", "contacts", "frame_contacts", "frame_residue_contacts", "interface_atoms", "irmsd", "interface_rigid_docking", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
+           "residue_centroids", "docking", "contacts", "frame_contacts", "frame_residue_contacts", "interface_atoms", "irmsd", "interface_rigid_docking", "hbonds", "frame_hbonds", "baker_hubbard",
+           "hydrogen_bonds", "unwrap_pbc", "atomic_masses", "hbond_tables", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch or the built library
@@ -32,4 +33,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         dk = importlib.import_module(".docking", __name__)
         return dk if name == "docking" else getattr(dk, name)
+    if name in ("hbonds", "frame_hbonds", "baker_hubbard", "hydrogen_bonds", "unwrap_pbc", "atomic_masses", "hbond_tables"):
+        import importlib
+        hb = importlib.import_module(".hbonds", __name__)
+        return hb if name == "hbonds" else getattr(hb, name)
     raise AttributeError(name)

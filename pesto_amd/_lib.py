@@ -70,7 +70,8 @@ ABI_SYMBOLS = [
     "pesto_trajectory_last_error", "pesto_contact_counts", "pesto_contact_loglik", "pesto_contact_div_kl", "pesto_residue_contact_maps",
     "pesto_native_contacts", "pesto_superpose", "pesto_residue_centroids", "pesto_sasa_last_error", "pesto_sasa",
     "pesto_dssp_last_error", "pesto_dssp", "pesto_docking_last_error", "pesto_frame_contacts", "pesto_frame_residue_contacts",
-    "pesto_interface_atoms", "pesto_rigid_docking", "pesto_interface_rmsd",
+    "pesto_interface_atoms", "pesto_rigid_docking", "pesto_interface_rmsd", "pesto_hbonds_last_error", "pesto_frame_hbonds",
+    "pesto_hbond_occupancy", "pesto_unwrap_pbc",
 ]
 
 _lib = None
@@ -164,22 +165,31 @@ def load():
     lib.pesto_interface_atoms.argtypes = [c_p, i64, c_p, i64, c_p, i64, c_p, c_p, i32, ctypes.c_float, ctypes.c_float, c_p, i32, c_p]
     lib.pesto_rigid_docking.argtypes = [c_p, i64, i64, i64, c_p, c_p, i64, c_p, i64, c_p, c_p, c_p, i32, c_p]
     lib.pesto_interface_rmsd.argtypes = [c_p, i64, i64, i64, c_p, c_p, i64, c_p, ctypes.c_double, c_p, i32, c_p]
+    lib.pesto_hbonds_last_error.restype = ctypes.c_char_p
+    lib.pesto_hbonds_last_error.argtypes = []
+    lib.pesto_frame_hbonds.argtypes = [c_p, i64, i64, i64, i64, c_p, c_p, c_p, c_p, ctypes.c_float, ctypes.c_float, ctypes.c_double, i64, c_p, c_p,
+                                       c_p, c_p, i32, c_p]
+    lib.pesto_hbond_occupancy.argtypes = [c_p, i64, i64, i64, i64, c_p, c_p, c_p, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_double,
+                                          i64, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_unwrap_pbc.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_stage_embed.argtypes = [c_p, i64, c_p, c_p]
     lib.pesto_stage_unpack.argtypes = [c_p, i64, i32, c_p, c_p, i32, c_p, c_p]
     lib.pesto_stage_layer.argtypes = [c_p, i32, c_p, c_p]
     lib.pesto_stage_pool.argtypes = [c_p, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p]
     for name in ABI_SYMBOLS:
         if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error",
-                        "pesto_trajectory_last_error", "pesto_sasa_last_error", "pesto_dssp_last_error", "pesto_docking_last_error"):
+                        "pesto_trajectory_last_error", "pesto_sasa_last_error", "pesto_dssp_last_error", "pesto_docking_last_error",
+                        "pesto_hbonds_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are eight channels:
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are nine channels:
     pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
-    pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error and pesto_docking_last_error."""
+    pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error, pesto_docking_last_error and
+    pesto_hbonds_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")

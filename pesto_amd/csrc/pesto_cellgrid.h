@@ -15,7 +15,8 @@
 // Build: k_grid_setup -> k_grid_count -> k_grid_scan -> k_grid_scatter, four launches; the users differ in what they check per atom in
 // the count pass and in the payload they scatter beside the coordinates, both functors.
 // (pesto_sasa.hip includes this header for struct_of and block_scan_exclusive only: its grid is another one, in double and per frame;
-// pesto_dssp.hip likewise: it has no grid.)
+// pesto_dssp.hip likewise: it has no grid; pesto_docking.hip and pesto_hbonds.hip take the list protocol's scans, k_frame_scan and
+// k_list_offsets.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,6 +77,48 @@ __device__ __forceinline__ int block_scan_exclusive(int* __restrict__ data, int 
         run += n;
     }
     return part[NT - 1];
+}
+
+// ---- the list protocol of pesto_docking.hip and pesto_hbonds.hip: count -> scan per frame -> 64-bit offsets -> emit
+constexpr int LIST_SCAN_NT = 1024;      // threads of the one workgroup that scans the frames' totals
+
+// the device counters of one call
+struct ListState {
+    long long K;      // list entries over all frames
+    int fits;         // K <= capacity: the emit pass runs
+    int err;          // error bits of the call's own index checks
+};
+
+// one workgroup per frame: the frame's n counts scanned in place (exclusive), their total to ftot[f]
+template <int NT>
+__global__ __launch_bounds__(NT) void k_frame_scan(int n, int* __restrict__ cnt, int* __restrict__ ftot) {
+    const int total = block_scan_exclusive<NT, false>(cnt + (size_t)blockIdx.x * n, n);
+    if (threadIdx.x == 0) ftot[blockIdx.x] = total;
+}
+
+// one workgroup: off[0 .. F] = exclusive scan of the frames' totals in 64 bits; K and whether it fits the capacity
+__global__ __launch_bounds__(LIST_SCAN_NT) void k_list_offsets(int F, const int* __restrict__ ftot, long long* __restrict__ off, long long cap,
+                                                               ListState* __restrict__ st) {
+    __shared__ long long part[LIST_SCAN_NT];
+    const int per = (F + LIST_SCAN_NT - 1) / LIST_SCAN_NT;
+    const int c0 = min(F, (int)threadIdx.x * per), c1 = min(F, c0 + per);
+    long long sum = 0;
+    for (int c = c0; c < c1; ++c) sum += ftot[c];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < LIST_SCAN_NT; o <<= 1) {
+        const long long v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    long long run = part[threadIdx.x] - sum;
+    for (int c = c0; c < c1; ++c) { off[c] = run; run += ftot[c]; }
+    if (threadIdx.x == LIST_SCAN_NT - 1) {
+        off[F] = part[LIST_SCAN_NT - 1];
+        st->K = part[LIST_SCAN_NT - 1];
+        st->fits = part[LIST_SCAN_NT - 1] <= cap ? 1 : 0;
+    }
 }
 
 // one workgroup per assembly: bounding box -> cell size and counts, cleared cell counters

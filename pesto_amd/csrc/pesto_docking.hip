@@ -13,24 +13,20 @@
 #include <cmath>
 
 #include "pesto_call.h"
-#include "pesto_cellgrid.h"      // (for block_scan_exclusive only: there is no cell grid here)
+#include "pesto_cellgrid.h"      // (for the list protocol's scans only: there is no cell grid here)
 #include "pesto_geom.h"
 
 namespace pesto {
 
 namespace {
 
-constexpr int NT = 256;                 // threads per workgroup of every kernel here but the offsets scan
+constexpr int NT = 256;                 // threads per workgroup of every kernel here
 constexpr int FC_ROWS = 8;              // frame contacts: atoms of A per wave (their partners' coordinates are loaded once for all of them)
 constexpr int FC_TILE = FC_ROWS * NT / 64;      // ... and per workgroup
-constexpr int SCAN_NT = 1024;           // threads of the one workgroup that scans the frames' totals
+constexpr int SCAN_NT = LIST_SCAN_NT;   // threads of the one workgroup that scans the frames' totals (k_list_offsets, pesto_cellgrid.h)
 
-// the device counters of one call
-struct DkState {
-    long long K;      // list entries over all frames
-    int fits;         // K <= capacity: the emit pass runs
-    int err;          // bit 0: an atom index outside its side; bit 1: a residue row outside 0 .. R - 1
-};
+// the device counters of one call (pesto_cellgrid.h); err bit 0: an atom index outside its side; bit 1: a residue row outside 0 .. R - 1
+using DkState = ListState;
 
 // ------------------------------------------------------------------------------------------------ frame contacts
 // replaces: the frame loop of contacts (md_analysis/mdtraj_utils/trajectory_utils.py:408-423; a dense [Na, Nb] matrix, torch.where and
@@ -85,36 +81,7 @@ __global__ __launch_bounds__(NT) void k_fc_pairs(int Na, int Nb, int tiles, cons
             if (i0 + r < Na) cnt[f * (size_t)Na + i0 + r] = n[r];
 }
 
-// one workgroup per frame: the frame's n counts scanned in place (exclusive), their total to ftot[f]
-__global__ __launch_bounds__(NT) void k_dk_frame_scan(int n, int* __restrict__ cnt, int* __restrict__ ftot) {
-    const int total = block_scan_exclusive<NT, false>(cnt + (size_t)blockIdx.x * n, n);
-    if (threadIdx.x == 0) ftot[blockIdx.x] = total;
-}
-
-// one workgroup: off[0 .. F] = exclusive scan of the frames' totals in 64 bits; K and whether it fits the capacity
-__global__ __launch_bounds__(SCAN_NT) void k_dk_offsets(int F, const int* __restrict__ ftot, long long* __restrict__ off, long long cap,
-                                                        DkState* __restrict__ st) {
-    __shared__ long long part[SCAN_NT];
-    const int per = (F + SCAN_NT - 1) / SCAN_NT;
-    const int c0 = min(F, (int)threadIdx.x * per), c1 = min(F, c0 + per);
-    long long sum = 0;
-    for (int c = c0; c < c1; ++c) sum += ftot[c];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 1; o < SCAN_NT; o <<= 1) {
-        const long long v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    long long run = part[threadIdx.x] - sum;
-    for (int c = c0; c < c1; ++c) { off[c] = run; run += ftot[c]; }
-    if (threadIdx.x == SCAN_NT - 1) {
-        off[F] = part[SCAN_NT - 1];
-        st->K = part[SCAN_NT - 1];
-        st->fits = part[SCAN_NT - 1] <= cap ? 1 : 0;
-    }
-}
+// (the per-frame scan k_frame_scan and the 64-bit offsets k_list_offsets: pesto_cellgrid.h)
 
 // ------------------------------------------------------------------------------------------------ residue contacts
 // replaces: atoms_to_residue_contacts (trajectory_utils.py:233-264; np.unique and a Python loop per frame and residue pair). Frame f owns
@@ -369,14 +336,7 @@ __global__ __launch_bounds__(NT) void k_rigid_docking(int Fr, int N, int nR, int
 }
 
 // ---- host side
-// the smallest float s whose distance fails `d < r_thr` (strict) or `d <= r_thr`: the test holds exactly for s < s_star
-float contact_threshold(float r_thr, float scale, bool strict) {
-    return first_true([=](float s) {
-        volatile float d = sqrt_rn(s) * scale;
-        return strict ? !(d < r_thr) : !(d <= r_thr);
-    });
-}
-
+// (contact_threshold, the smallest float s whose distance fails the test: pesto_geom.h)
 int check_cutoff(float r_thr, float scale) {
     if (!std::isfinite(r_thr) || !std::isfinite(scale) || !(scale > 0.f)) return fail(PESTO_ERR_INVALID, "r_thr must be finite and scale positive and finite");
     return 0;
@@ -415,8 +375,8 @@ int pesto_frame_contacts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
         const dim3 grid((unsigned)(F * tiles));
         hipLaunchKernelGGL(k_fc_pairs<false>, grid, dim3(NT), 0, bf.stm, (int)Na, (int)Nb, (int)tiles, bf.ptr<const float>(iA), bf.ptr<const float>(iB),
                            s_star, scale, bf.ptr<int>(iCnt), (const long long*)nullptr, (const DkState*)nullptr, (int*)nullptr, (float*)nullptr);
-        hipLaunchKernelGGL(k_dk_frame_scan, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)Na, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
-        hipLaunchKernelGGL(k_dk_offsets, dim3(1), dim3(SCAN_NT), 0, bf.stm, (int)F, bf.ptr<const int>(iTot), bf.ptr<long long>(iO),
+        hipLaunchKernelGGL(k_frame_scan<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)Na, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
+        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(SCAN_NT), 0, bf.stm, (int)F, bf.ptr<const int>(iTot), bf.ptr<long long>(iO),
                            (long long)cap_pairs, bf.ptr<DkState>(iSt));
         hipLaunchKernelGGL(k_fc_pairs<true>, grid, dim3(NT), 0, bf.stm, (int)Na, (int)Nb, (int)tiles, bf.ptr<const float>(iA), bf.ptr<const float>(iB),
                            s_star, scale, bf.ptr<int>(iCnt), bf.ptr<const long long>(iO), bf.ptr<const DkState>(iSt), bf.ptr<int>(iP),
@@ -468,8 +428,8 @@ int pesto_frame_residue_contacts(pesto_model* m, int64_t F, int64_t Na, int64_t 
             hipLaunchKernelGGL(k_rc_mark, dim3(blocks(Kz)), dim3(NT), 0, bf.stm, (long long)K, (int)F, (int)Na, (int)Nb, Ra, Rb, (int)W, off, pr, ra, rb, st,
                                bf.ptr<unsigned>(iBits));
         hipLaunchKernelGGL(k_rc_count, dim3(blocks(n_words)), dim3(NT), 0, bf.stm, n_words, bf.ptr<const unsigned>(iBits), bf.ptr<int>(iCnt));
-        hipLaunchKernelGGL(k_dk_frame_scan, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)W, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
-        hipLaunchKernelGGL(k_dk_offsets, dim3(1), dim3(SCAN_NT), 0, bf.stm, (int)F, bf.ptr<const int>(iTot), bf.ptr<long long>(iO),
+        hipLaunchKernelGGL(k_frame_scan<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)W, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
+        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(SCAN_NT), 0, bf.stm, (int)F, bf.ptr<const int>(iTot), bf.ptr<long long>(iO),
                            (long long)cap_rpairs, st);
         hipLaunchKernelGGL(k_rc_emit, dim3(blocks(n_words)), dim3(NT), 0, bf.stm, n_words, (int)W, Rb, bf.ptr<const unsigned>(iBits),
                            bf.ptr<const int>(iCnt), bf.ptr<const long long>(iO), (const DkState*)st, bf.ptr<int>(iRp), bf.ptr<unsigned>(iDm));

@@ -1,4 +1,4 @@
-// pesto_geom.h - the geometry the MD analysis groups share (pesto_trajectory.hip, pesto_docking.hip): the float32 squared distance of
+// pesto_geom.h - the geometry the MD analysis groups share (pesto_trajectory.hip, pesto_docking.hip, pesto_hbonds.hip): the float32 squared distance of
 // NumPy and torch, the host's derivation of squared-distance thresholds from it, the workgroup sum in double and the rotation of a
 // Kabsch superposition.
 //
@@ -117,6 +117,15 @@ template <class Pred> float first_true(Pred pred) {
 }
 
 float sqrt_rn(float s) { volatile float r = std::sqrt(s); return r; }
+
+// the smallest float s whose distance fl32(sqrt_rn(s)) * scale fails `d < r_thr` (strict) or `d <= r_thr`: the test holds exactly for
+// s < s_star (the product is monotonic in s)
+float contact_threshold(float r_thr, float scale, bool strict) {
+    return first_true([=](float s) {
+        volatile float d = sqrt_rn(s) * scale;
+        return strict ? !(d < r_thr) : !(d <= r_thr);
+    });
+}
 
 
 }  // namespace
