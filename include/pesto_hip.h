@@ -562,7 +562,8 @@ int pesto_hbond_occupancy(pesto_model* m, int64_t F, int64_t N, int64_t P, int64
                           int64_t* sizes_out, int32_t ptr_kind, void* stream);
 
 /* replaces: unwrap_pbc (trajectory_utils.py:28-64; a Python loop over chains and their 27 periodic images, a copy of the trajectory).
- * xyz [F,N,3]; unitcell_lengths float32 [F,3]; perm int32 [N]: the atoms ordered by molecule (in [0, N), else PESTO_ERR_INVALID);
+ * xyz [F,N,3]; unitcell_lengths float32 [F,3]; perm int32 [N]: the atoms ordered by molecule, a permutation of [0, N) (an index outside
+ * [0, N) or named twice: PESTO_ERR_INVALID, checked on the device before anything is read through it);
  * mol_off int32 [M+1] (HOST): molecule m holds perm[mol_off[m] .. mol_off[m+1]), none empty; masses float64 [N]. In double:
  *     com[f,m] = sum(mass x) / sum(mass) over the molecule, in a fixed order
  *     for m >= 1, image k = 0 .. 26 is dV[k] = (g[(k/3)%3], g[k/9], g[k%3]), g = (0, 1, -1): y slowest, then x, then z

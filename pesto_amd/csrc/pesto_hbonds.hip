@@ -29,8 +29,9 @@ constexpr int HB_ROWS = 8;                              // donor pairs per wave 
 constexpr int HB_TILE = HB_ROWS * NT / 64;              // ... and per workgroup
 static_assert(HB_TILE == PESTO_HBONDS_DONOR_TILE, "the header states the donor tile");
 
-// err of the call's ListState: bit 0: an atom of dh outside [0, N); bit 1: an atom of acc; bit 2: an atom of the molecule permutation
-enum { ERR_DH = 1, ERR_ACC = 2, ERR_PERM = 4 };
+// err of the call's ListState: bit 0: an atom of dh outside [0, N); bit 1: an atom of acc; bit 2: an atom of the molecule permutation;
+// bit 3: an atom named twice by the molecule permutation (some other atom is then named by no row, and its output never written)
+enum { ERR_DH = 1, ERR_ACC = 2, ERR_PERM = 4, ERR_DUP = 8 };
 
 // the angle criterion at H: u = D - H (u[0..2], u[3] = uu), v = A - H
 __device__ __forceinline__ double dot3_rn(double ax, double ay, double az, double bx, double by, double bz) {
@@ -186,9 +187,13 @@ __global__ __launch_bounds__(NT) void k_hb_occupancy(int F, int N, int P, int A,
 // replaces: unwrap_pbc (trajectory_utils.py:28-64; 27 images of every chain's centre of mass in a Python loop over chains and images, a
 // copy of the trajectory). Molecule m holds the atoms perm[off[m] .. off[m + 1]).
 
-__global__ __launch_bounds__(NT) void k_uw_check(int N, const int* __restrict__ perm, ListState* __restrict__ st) {
+// perm must be a permutation of [0, N): every entry in range, and (N entries for N atoms) none named twice; seen[N] starts at zero
+__global__ __launch_bounds__(NT) void k_uw_check(int N, const int* __restrict__ perm, int* __restrict__ seen, ListState* __restrict__ st) {
     const int i = blockIdx.x * NT + threadIdx.x;
-    if (i < N && (perm[i] < 0 || perm[i] >= N)) atomicOr(&st->err, ERR_PERM);
+    if (i >= N) return;
+    const int a = perm[i];
+    if (a < 0 || a >= N) atomicOr(&st->err, ERR_PERM);
+    else if (atomicAdd(&seen[a], 1) != 0) atomicOr(&st->err, ERR_DUP);
 }
 
 // one workgroup per (frame, molecule): com[f, m] = sum(mass x) / sum(mass) in double, thread t taking the atoms t, t + NT, ... of the
@@ -388,14 +393,15 @@ int pesto_unwrap_pbc(pesto_model* m, int64_t F, int64_t N, int64_t M, const floa
     const int iX = bf.input(xyz, (size_t)F * N * 12), iL = bf.input(unitcell_lengths, (size_t)F * 12), iP = bf.input(perm, (size_t)N * 4),
               iOf = bf.table(mol_off, ((size_t)M + 1) * 4), iMs = bf.input(masses, (size_t)N * 8);
     const int iY = bf.output(xyz_out, (size_t)F * N * 12), iIm = bf.output(image_out, (size_t)F * M * 4);
-    const int iSt = bf.scratch(sizeof(ListState)), iCm = bf.scratch((size_t)F * M * 24);
+    const int iSt = bf.scratch(sizeof(ListState)), iCm = bf.scratch((size_t)F * M * 24), iSeen = bf.scratch((size_t)N * 4);
     ListState hs = {};
     int rc = bf.upload();
     if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<ListState>(iSt), 0, sizeof(ListState), bf.stm), "unwrap_pbc");
+    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSeen), 0, (size_t)N * 4, bf.stm), "unwrap_pbc");
     if (rc == 0) {
         const dim3 grid((unsigned)(F * M));
         ListState* st = bf.ptr<ListState>(iSt);
-        hipLaunchKernelGGL(k_uw_check, dim3(blocks((size_t)N)), dim3(NT), 0, bf.stm, (int)N, bf.ptr<const int>(iP), st);
+        hipLaunchKernelGGL(k_uw_check, dim3(blocks((size_t)N)), dim3(NT), 0, bf.stm, (int)N, bf.ptr<const int>(iP), bf.ptr<int>(iSeen), st);
         hipLaunchKernelGGL(k_uw_com, grid, dim3(NT), 0, bf.stm, (int)N, (int)M, bf.ptr<const float>(iX), bf.ptr<const int>(iP), bf.ptr<const int>(iOf),
                            bf.ptr<const double>(iMs), (const ListState*)st, bf.ptr<double>(iCm));
         hipLaunchKernelGGL(k_uw_shift, grid, dim3(NT), 0, bf.stm, (int)N, (int)M, bf.ptr<const float>(iX), bf.ptr<const float>(iL), bf.ptr<const int>(iP),
@@ -404,6 +410,7 @@ int pesto_unwrap_pbc(pesto_model* m, int64_t F, int64_t N, int64_t M, const floa
     }
     if (rc == 0) rc = bf.read(iSt, &hs, sizeof(ListState));
     rc = bf.finish(rc, "unwrap_pbc");
-    if (rc == 0 && hs.err) rc = fail(PESTO_ERR_INVALID, "perm: atom indices must lie in [0, N)");
+    if (rc == 0 && (hs.err & ERR_PERM)) rc = fail(PESTO_ERR_INVALID, "perm: atom indices must lie in [0, N)");
+    if (rc == 0 && (hs.err & ERR_DUP)) rc = fail(PESTO_ERR_INVALID, "perm: every atom must be named once (an index is repeated)");
     return rc;
 }

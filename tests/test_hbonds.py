@@ -222,3 +222,14 @@ def test_indices_outside_the_topology_are_refused():
     rc = lib.pesto_unwrap_pbc(model.handle, 3, 10, 3, ux.ctypes.data, ub.ctypes.data, perm.ctypes.data, moff.ctypes.data, u["masses"].ctypes.data,
                               out.ctypes.data, image.ctypes.data, _lib.PTR_HOST, None)
     assert rc == -1 and b"[0, N)" in lib.pesto_hbonds_last_error()
+    # in range but not a permutation: atom perm[4] twice, atom perm[3] never, whose rows of xyz_out no molecule would write
+    perm = np.argsort(u["mol"], kind="stable").astype(np.int32)
+    perm[3] = perm[4]
+    rc = lib.pesto_unwrap_pbc(model.handle, 3, 10, 3, ux.ctypes.data, ub.ctypes.data, perm.ctypes.data, moff.ctypes.data, u["masses"].ctypes.data,
+                              out.ctypes.data, image.ctypes.data, _lib.PTR_HOST, None)
+    assert rc == -1 and b"repeated" in lib.pesto_hbonds_last_error() and b"[0, N)" not in lib.pesto_hbonds_last_error()
+    perm = np.argsort(u["mol"], kind="stable").astype(np.int32)[::-1].copy()     # any order within a molecule's range is a permutation still
+    perm[:] = np.concatenate([perm[8:], perm[4:8], perm[:4]])
+    rc = lib.pesto_unwrap_pbc(model.handle, 3, 10, 3, ux.ctypes.data, ub.ctypes.data, perm.ctypes.data, moff.ctypes.data, u["masses"].ctypes.data,
+                              out.ctypes.data, image.ctypes.data, _lib.PTR_HOST, None)
+    assert rc == 0 and np.array_equal(image, g["uplanted_image"]) and np.array_equal(out.view(np.uint32), g["uplanted_out"].view(np.uint32))
