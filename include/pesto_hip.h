@@ -669,6 +669,50 @@ int pesto_stage_layer(pesto_model* m, int32_t layer, float* q_io, float* p_io);
 int pesto_stage_pool(pesto_model* m, int64_t N, int64_t R, const float* q, const float* p, const int32_t* res_of_atom,
                      float* qr_out /*[R,32]*/, float* pr_out /*[R,3,32]*/, float* z_out /*[R,n_out]*/);
 
+/* ---- training step (pesto_train.hip) ----
+ * replaces: eval_step + loss.backward() + optimizer.step() (model/main.py:42-58, 186-200) with torch.optim.Adam at its defaults, all in
+ * float32: the forward runs on the exact fp32 layer kernel and keeps the input state of every layer ((n_layers + 1) x (N + 1) x 128
+ * floats), the backward recomputes each layer from its inputs as the reference's checkpoint does (src/model_operations.py:234-236).
+ * A trainer is a handle of its own (weights in blob order, Adam's m and v, pos_ratios and the plain section of the weight image on the
+ * device); failures are reported through pesto_train_last_error() (thread-local). em_depth / dm_depth = 1 is rejected.
+ * Sums that several workgroups add to (weight gradients, the scatter-add of the gather) are accumulated with 64-bit fixed-point atomics
+ * (40 fractional bits; terms clamped to +-4e6, sums wrap beyond +-2^23): they do not depend on the order of the workgroups, so the
+ * same step gives the same bits on every run. */
+typedef struct pesto_trainer pesto_trainer;
+const char* pesto_train_last_error(void);
+/* pos_ratios = 0.5, global_step = 0 (model/main.py:134-136) */
+int pesto_train_create(const pesto_config* cfg, const float* weights, int64_t n_weights, int device, float lr, float pos_weight_factor,
+                       pesto_trainer** out);
+int pesto_train_destroy(pesto_trainer* t);
+/* One collated batch with pesto_forward's semantics (the call's last atom as wrap target, the call-global max(D)).
+ * mode 0: eval_step (main.py:42-58; pos_ratios updated, no gradient); 1: the same plus the gradient of sum(losses) with respect to
+ * every parameter, handed out in blob order (grads_out, n_weights floats); 2: global_step += 1, then mode 1 and the Adam update.
+ * y [R,C] float 0/1 with C == n_out; losses_out, p_out (= sigmoid(z)) and z_out [R,C] may be NULL. ids in [0, N], res_of_atom in [0, R)
+ * with no empty residue: checked on the device BEFORE any other kernel runs (PESTO_ERR_INVALID; the trainer's state is untouched). */
+int pesto_train_step(pesto_trainer* t, int32_t mode, int64_t N, int64_t R, int32_t k, int32_t C, const float* X, const void* ids_topk,
+                     int32_t ids_kind, const float* q0, const int32_t* res_of_atom, const float* y, float* losses_out, float* p_out,
+                     float* z_out, float* grads_out, int32_t ptr_kind, void* stream);
+/* torch.optim.Adam.step() (betas 0.9 / 0.999, eps 1e-8, bias correction) with a gradient given in blob order (host pointer) */
+int pesto_train_adam(pesto_trainer* t, const float* grads);
+/* host copies of the trainer's state; a NULL argument is skipped */
+int pesto_train_get_state(pesto_trainer* t, float* weights_out, float* pos_ratios_out /*[n_out]*/, int64_t* global_step, float* lr);
+int pesto_train_set_state(pesto_trainer* t, const float* pos_ratios /*[n_out]*/, const int64_t* global_step, const float* lr);
+/* HIP-event times of the last pesto_train_step (ms): forward + loss, backward, Adam; enabled != 0 makes the steps record them */
+int pesto_train_set_timing(pesto_trainer* t, int32_t enabled);
+int pesto_train_get_timing(pesto_trainer* t, double* ms_out /*[3]*/);
+/* per-stage backward entry points (HOST pointers), used by tests/: gradients in blob order (n_weights floats, zero outside the stage)
+ * replaces: the backward of em.forward (model/model.py:34); dq [N,32] */
+int pesto_train_stage_embed(pesto_trainer* t, int64_t N, const float* q0, const float* dq, float* grads_out);
+/* replaces: the backward of StateUpdateLayer.forward (src/model_operations.py:225-242) of layer `layer`: states and their gradients
+ * [N+1,32] / [N+1,3,32] with the sink row, whose output gradient is multiplied by 0 (:239-240) */
+int pesto_train_stage_layer(pesto_trainer* t, int32_t layer, int64_t N, int32_t k, const float* X, const void* ids_topk, int32_t ids_kind,
+                            const float* q_in, const float* p_in, const float* dq_out, const float* dp_out, float* dq_in, float* dp_in,
+                            float* grads_out);
+/* replaces: the backward of StatePoolLayer.forward + decoder (src/model_operations.py:197-213, model/model.py:46-50); q [N,32],
+ * p [N,3,32] without the sink row, dz [R,n_out] */
+int pesto_train_stage_head(pesto_trainer* t, int64_t N, int64_t R, const float* q, const float* p, const int32_t* res_of_atom,
+                           const float* dz, float* dq, float* dp, float* grads_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,9 @@ ABI_SYMBOLS = [
     "pesto_dssp_last_error", "pesto_dssp", "pesto_docking_last_error", "pesto_frame_contacts", "pesto_frame_residue_contacts",
     "pesto_interface_atoms", "pesto_rigid_docking", "pesto_interface_rmsd", "pesto_hbonds_last_error", "pesto_frame_hbonds",
     "pesto_hbond_occupancy", "pesto_unwrap_pbc",
+    "pesto_train_last_error", "pesto_train_create", "pesto_train_destroy", "pesto_train_step", "pesto_train_adam", "pesto_train_get_state",
+    "pesto_train_set_state", "pesto_train_set_timing", "pesto_train_get_timing", "pesto_train_stage_embed", "pesto_train_stage_layer",
+    "pesto_train_stage_head",
 ]
 
 _lib = None
@@ -172,6 +175,19 @@ def load():
     lib.pesto_hbond_occupancy.argtypes = [c_p, i64, i64, i64, i64, c_p, c_p, c_p, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_double,
                                           i64, c_p, c_p, c_p, i32, c_p]
     lib.pesto_unwrap_pbc.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_train_last_error.restype = ctypes.c_char_p
+    lib.pesto_train_last_error.argtypes = []
+    lib.pesto_train_create.argtypes = [P(PestoConfig), c_p, i64, ctypes.c_int, ctypes.c_float, ctypes.c_float, P(c_p)]
+    lib.pesto_train_destroy.argtypes = [c_p]
+    lib.pesto_train_step.argtypes = [c_p, i32, i64, i64, i32, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_train_adam.argtypes = [c_p, c_p]
+    lib.pesto_train_get_state.argtypes = [c_p, c_p, c_p, P(i64), P(ctypes.c_float)]
+    lib.pesto_train_set_state.argtypes = [c_p, c_p, P(i64), P(ctypes.c_float)]
+    lib.pesto_train_set_timing.argtypes = [c_p, i32]
+    lib.pesto_train_get_timing.argtypes = [c_p, P(ctypes.c_double)]
+    lib.pesto_train_stage_embed.argtypes = [c_p, i64, c_p, c_p, c_p]
+    lib.pesto_train_stage_layer.argtypes = [c_p, i32, i64, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+    lib.pesto_train_stage_head.argtypes = [c_p, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
     lib.pesto_stage_embed.argtypes = [c_p, i64, c_p, c_p]
     lib.pesto_stage_unpack.argtypes = [c_p, i64, i32, c_p, c_p, i32, c_p, c_p]
     lib.pesto_stage_layer.argtypes = [c_p, i32, c_p, c_p]
@@ -179,17 +195,17 @@ def load():
     for name in ABI_SYMBOLS:
         if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error",
                         "pesto_trajectory_last_error", "pesto_sasa_last_error", "pesto_dssp_last_error", "pesto_docking_last_error",
-                        "pesto_hbonds_last_error"):
+                        "pesto_hbonds_last_error", "pesto_train_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are nine channels:
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are ten channels:
     pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
-    pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error, pesto_docking_last_error and
-    pesto_hbonds_last_error."""
+    pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error, pesto_docking_last_error,
+    pesto_hbonds_last_error and pesto_train_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")
