@@ -692,6 +692,29 @@ int pesto_train_destroy(pesto_trainer* t);
 int pesto_train_step(pesto_trainer* t, int32_t mode, int64_t N, int64_t R, int32_t k, int32_t C, const float* X, const void* ids_topk,
                      int32_t ids_kind, const float* q0, const int32_t* res_of_atom, const float* y, float* losses_out, float* p_out,
                      float* z_out, float* grads_out, int32_t ptr_kind, void* stream);
+/* ---- the same forward and backward for a caller's own loss and optimiser (pesto_amd.nn: a torch Module over this handle) ----
+ * replaces: model.parameters() handed to an optimiser that updates them in place (model/main.py:159, 200), load_state_dict (:150).
+ * The weights are taken from a blob in pesto_amd.weights order (host or device pointer, n_weights floats) and the plain section of the
+ * weight image is refreshed from it; Adam's m / v, pos_ratios and global_step are untouched. */
+int pesto_train_set_weights(pesto_trainer* t, const float* blob, int32_t ptr_kind, void* stream);
+/* replaces: z = model.forward(X, ids_topk, q, M) (model/main.py:46, model/model.py:32-52) without a loss: the argument check and the
+ * kernels of pesto_train_step's forward half, so z_out [R,n_out] has its bits; pos_ratios and global_step are untouched.
+ * keep != 0 keeps the input state of every layer for one pesto_train_backward and hands out a ticket (*ticket_out: 1, 2, ... per handle);
+ * keep == 0 runs on two alternating states (ticket_out may be NULL). A handle has ONE workspace: every later forward, training step,
+ * stage call or weight update ends the ticket. With device pointers X, q0 and res_of_atom must stay alive and unchanged until the
+ * backward has run (it reads them again); host arrays are copied. */
+int pesto_train_forward(pesto_trainer* t, int32_t keep, int64_t N, int64_t R, int32_t k, const float* X, const void* ids_topk, int32_t ids_kind,
+                        const float* q0, const int32_t* res_of_atom, float* z_out, int64_t* ticket_out, int32_t ptr_kind, void* stream);
+/* replaces: z.backward(dz) (model/main.py:196-199 with a caller's loss; X.requires_grad_() / q.requires_grad_() for the input gradients).
+ * dz [R,n_out]; grads_out: the parameter gradients in blob order (n_weights floats); dq0_out [N,n0] and dX_out [N,3]; each of the three
+ * may be NULL and is then not computed. A ticket that is not the handle's last kept forward fails with PESTO_ERR_INVALID: a gradient of
+ * another forward is never produced. The call may be repeated on the same ticket (retain_graph) and gives the same bits.
+ * dX is the backward of unpack_state_features (src/model_operations.py:8-14) under every layer's use of D and R (:109-116, 131-136):
+ * d|r|/dr = 0 at r = 0 as in torch; the fix-up mask (D < 1e-2) is the forward's own decision; the gradient of max(D) is split evenly over
+ * the maximal edges, which for one edge or the two directions of one pair equals any other rule - other exact ties of the maximum are
+ * undefined in the reference's gradient as well. */
+int pesto_train_backward(pesto_trainer* t, int64_t ticket, const float* dz, float* grads_out, float* dq0_out, float* dX_out, int32_t ptr_kind,
+                         void* stream);
 /* torch.optim.Adam.step() (betas 0.9 / 0.999, eps 1e-8, bias correction) with a gradient given in blob order (host pointer) */
 int pesto_train_adam(pesto_trainer* t, const float* grads);
 /* host copies of the trainer's state; a NULL argument is skipped */

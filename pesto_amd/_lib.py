@@ -74,7 +74,7 @@ ABI_SYMBOLS = [
     "pesto_hbond_occupancy", "pesto_unwrap_pbc",
     "pesto_train_last_error", "pesto_train_create", "pesto_train_destroy", "pesto_train_step", "pesto_train_adam", "pesto_train_get_state",
     "pesto_train_set_state", "pesto_train_set_timing", "pesto_train_get_timing", "pesto_train_stage_embed", "pesto_train_stage_layer",
-    "pesto_train_stage_head",
+    "pesto_train_stage_head", "pesto_train_set_weights", "pesto_train_forward", "pesto_train_backward",
 ]
 
 _lib = None
@@ -181,6 +181,9 @@ def load():
     lib.pesto_train_destroy.argtypes = [c_p]
     lib.pesto_train_step.argtypes = [c_p, i32, i64, i64, i32, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_train_adam.argtypes = [c_p, c_p]
+    lib.pesto_train_set_weights.argtypes = [c_p, c_p, i32, c_p]
+    lib.pesto_train_forward.argtypes = [c_p, i32, i64, i64, i32, c_p, c_p, i32, c_p, c_p, c_p, P(i64), i32, c_p]
+    lib.pesto_train_backward.argtypes = [c_p, i64, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_train_get_state.argtypes = [c_p, c_p, c_p, P(i64), P(ctypes.c_float)]
     lib.pesto_train_set_state.argtypes = [c_p, c_p, P(i64), P(ctypes.c_float)]
     lib.pesto_train_set_timing.argtypes = [c_p, i32]

@@ -1,6 +1,6 @@
 // pesto_geom.h - the geometry the MD analysis groups share (pesto_trajectory.hip, pesto_docking.hip, pesto_hbonds.hip): the float32 squared distance of
 // NumPy and torch, the host's derivation of squared-distance thresholds from it, the workgroup sum in double and the rotation of a
-// Kabsch superposition.
+// Kabsch superposition. Also one edge of the model's geometry (r, |r|, the fix-up) for the backward of the geometry pass (pesto_train.hip).
 //
 // Everything sits in an anonymous namespace (one copy per translation unit, like pesto_call.h).
 #pragma once
@@ -20,6 +20,19 @@ __device__ __forceinline__ float dist2(float ax, float ay, float az, float bx, f
     const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
+
+
+// One edge of the model's geometry (src/model_operations.py:8-14) in the float32 operations of the forward's geometry pass (k_unpack1 /
+// k_unpack2, pesto_kernels.hip, whose text is pinned by the committed profile's source stamp): the same expressions with the same
+// explicit FMAs, so the backward (pesto_train.hip) gets the forward's bits of D0 and makes the forward's fix-up decision.
+// r = X_j - X_i, returns D0 = |r| (torch.norm's FMA chain)
+__device__ __forceinline__ float edge_vec(const float* __restrict__ xj, const float* __restrict__ xi, float& rx, float& ry, float& rz) {
+    rx = xj[0] - xi[0]; ry = xj[1] - xi[1]; rz = xj[2] - xi[2];
+    return sqrtf(fmaf(rz, rz, fmaf(ry, ry, rx * rx)));
+}
+// the fix-up of :12: an edge shorter than 1e-2 gets the call's maximal distance added
+__device__ __forceinline__ bool edge_fixup(float d0) { return d0 < 1e-2f; }
+__device__ __forceinline__ float edge_dist(float d0, float dmax) { return d0 + dmax * (edge_fixup(d0) ? 1.0f : 0.0f); }
 
 
 // sum of v over the workgroup, the same bits in every thread: butterfly within each wave, then the four waves in turn.

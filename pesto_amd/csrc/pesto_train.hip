@@ -6,6 +6,8 @@
 //   backward + optimiser step           model/main.py:186-200 (torch.optim.Adam defaults)
 //   state-update layer                  src/model_operations.py:87-154, checkpointed :234-236, sink reset :239-240
 //   residue pool + decoder              src/model_operations.py:197-213, model/model.py:46-50
+//   geometry (for d X)                  src/model_operations.py:6-22
+//   autograd use (caller's d z)         model/main.py:159, 196-200: a torch Module's forward / backward (pesto_amd.nn)
 //
 // The backward mirrors the forward kernels phase by phase: a kernel recomputes its stage from the stage's inputs, keeps every
 // activation in LDS and walks the phases in reverse. Gradients are accumulated in the layout of the PLAIN section of the device weight
@@ -19,6 +21,7 @@
 #include <new>
 
 #include "pesto_call.h"
+#include "pesto_geom.h"
 #include "pesto_kernels.h"
 
 namespace pesto {
@@ -373,9 +376,10 @@ __global__ __launch_bounds__(256) void k_head_sam_bwd(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------- embed backward
-// 8 atoms per workgroup: em forward again from q0, weight gradients from dq (state row i + 1); q0 carries no gradient
+// 8 atoms per workgroup: em forward again from q0, weight gradients from dq (state row i + 1). dq0_out (may be null) [N][n0] receives
+// d q0 = d h1 . W_em.0, the gradient of the input features (the reference's q.requires_grad_(), model/model.py:34)
 __global__ __launch_bounds__(256) void k_embed_bwd(const float* __restrict__ W, fx_t* __restrict__ G, MlpW em, int N, int n0,
-                                                   const float* __restrict__ q0, const float* __restrict__ dq_state) {
+                                                   const float* __restrict__ q0, const float* __restrict__ dq_state, float* __restrict__ dq0_out) {
     __shared__ float xs[8][512];
     __shared__ float h1[8][32], h2[8][32], d1[8][32], d2[8][32], dy[8][32];
     const int g = threadIdx.x >> 5, s = threadIdx.x & 31;
@@ -387,7 +391,9 @@ __global__ __launch_bounds__(256) void k_embed_bwd(const float* __restrict__ W, 
     }
     __syncthreads();
     mlp3_hidden(W, em, &xs[0][0], 512, &h1[0][0], &h2[0][0], rows);
-    mlp3_bwd(W, G, em, &xs[0][0], 512, &h1[0][0], &h2[0][0], &dy[0][0], 32, &d2[0][0], &d1[0][0], nullptr, 0, rows);
+    mlp3_bwd(W, G, em, &xs[0][0], 512, &h1[0][0], &h2[0][0], &dy[0][0], 32, &d2[0][0], &d1[0][0], dq0_out ? &xs[0][0] : nullptr, 512, rows);
+    if (dq0_out && g < rows)
+        for (int k = s; k < n0; k += 32) dq0_out[(size_t)i * n0 + k] = xs[g][k];
 }
 
 // ---------------------------------------------------------------------------------------------- layer backward
@@ -445,14 +451,19 @@ __device__ __forceinline__ void edge_bgrad(fx_t* __restrict__ G, int goff, const
     }
 }
 
-template <int NN>
+// GEO = true also forms the gradient of every edge's geometry, (d r^_x, d r^_y, d r^_z, d d), from the four places it enters the layer
+// (src/model_operations.py:109-116, 131-136): the distance column of X_e, p_i.r^ and p_j.r^, and V[:,1] (x) r^ of Vp. It is staged per
+// edge row in dgs (1 KB of LDS on top of LayerBwdSmem) and added into dgeo [(N+1)][KMAX]: a centre's slots belong to one workgroup and
+// the stream runs layer after layer, so the read-add-write is plain and in a fixed order. GEO = false is the kernel without any of it.
+template <int NN, bool GEO>
 __global__ __launch_bounds__(256) void k_layer_v1_bwd(const float* __restrict__ W, fx_t* __restrict__ G, LayerW lw, int N1,
                                                       const int* __restrict__ ids_s, const float4* __restrict__ geo,
                                                       const float* __restrict__ q_in, const float* __restrict__ p_in,
                                                       const fx_t* __restrict__ dq_out, const fx_t* __restrict__ dp_out,
-                                                      fx_t* __restrict__ dq_in, fx_t* __restrict__ dp_in) {
+                                                      fx_t* __restrict__ dq_in, fx_t* __restrict__ dp_in, float4* __restrict__ dgeo) {
     constexpr int A = 64 / NN;
     __shared__ LayerBwdSmem sm;
+    __shared__ float4 dgs[GEO ? 64 : 1];
     const int t = threadIdx.x;
     const int c0 = blockIdx.x * A;
     const float sdk = sqrtf((float)NK);
@@ -677,16 +688,23 @@ __global__ __launch_bounds__(256) void k_layer_v1_bwd(const float* __restrict__ 
             }
         } else {
             const int j = sm.nb[ar];
+            float tg[3] = {0.f, 0.f, 0.f};      // GEO: the edge's term of Zp contracted with V1 instead of r^
+            const float lg0 = sm.lg[(0 * 4 + 1) * 64 + ar], lg1 = sm.lg[(1 * 4 + 1) * 64 + ar];
             for (int x = 0; x < 3; ++x) {
                 const float gx = x == 0 ? g.x : (x == 1 ? g.y : g.z);
                 for (int s = 0; s < 32; ++s) {
                     float v;
-                    if (apart == 1) v = kv[(44 + s) * LD + ar] * gx;
+                    if (apart == 1) {
+                        v = kv[(44 + s) * LD + ar] * gx;
+                        if constexpr (GEO) tg[x] += (lg0 * dz[64 * (1 + x) + s] + lg1 * dz[64 * (1 + x) + 32 + s]) * kv[(44 + s) * LD + ar];
+                    }
                     else if (apart == 2) v = sm.pis[aa * 96 + 32 * x + s];
                     else v = p_in[(size_t)j * 96 + 32 * x + s];
                     dm[0] += dz[64 * (1 + x) + s] * v; dm[1] += dz[64 * (1 + x) + 32 + s] * v;
                 }
             }
+            if constexpr (GEO)
+                if (apart == 1) dgs[ar] = make_float4(tg[0], tg[1], tg[2], 0.0f);
         }
         sm.dl[(0 * 4 + apart) * 64 + ar] = dm[0];
         sm.dl[(1 * 4 + apart) * 64 + ar] = dm[1];
@@ -847,7 +865,14 @@ __global__ __launch_bounds__(256) void k_layer_v1_bwd(const float* __restrict__ 
         for (int oo = 0; oo < 128; ++oo) { const float c = sm.cpart[ca * 128 + oo]; v0 += w0[oo] * c; v1 += w1[oo] * c; }
         cq += v0; cn += v1;
     }
-    {   // d xe in place: row 1 + o (row 0, the distance, carries no gradient)
+    if constexpr (GEO) {   // row 0 of d xe, the distance: sum_k W1[0][k] d h1[k][edge] (dgs[t].xyz was written in the attention phase)
+        if (t < 64) {
+            float v = 0.0f;
+            for (int k = 0; k < 128; ++k) v += W[lw.w1 + k] * sm.h1[k * LD + t];
+            dgs[t].w = v;
+        }
+    }
+    {   // d xe in place: row 1 + o (row 0, the distance, is formed above and only under GEO)
         const float* wr = W + lw.w1 + (65 + o) * 128;
 #pragma unroll
         for (int m = 0; m < 32; ++m) acc[m] = 0.0f;
@@ -872,6 +897,23 @@ __global__ __launch_bounds__(256) void k_layer_v1_bwd(const float* __restrict__ 
         for (int it = 0; it < 8; ++it) {
             const int r = rg + 8 * it, a = r / NN, i = c0 + a;
             const int j = sm.nb[r];
+            if constexpr (GEO) {   // p_i.r^ and p_j.r^: rows 65..128 of d xe times p_i / p_j, summed over the 32 channels of the row
+                const bool iv = i < N1 && i != 0;      // (a padded slot, j == 0, has a real geometry: X[-1], model_operations.py:8)
+                float gv[3];
+#pragma unroll
+                for (int x = 0; x < 3; ++x)
+                    gv[x] = iv ? sm.xe[(65 + s) * LD + r] * sm.pis[a * 96 + 32 * x + s] + sm.xe[(97 + s) * LD + r] * p_in[(size_t)j * 96 + 32 * x + s] : 0.0f;
+#pragma unroll
+                for (int x = 0; x < 3; ++x)
+                    for (int off = 16; off > 0; off >>= 1) gv[x] += __shfl_xor(gv[x], off);      // (within the row's 32 lanes)
+                if (iv && s == 0) {
+                    const float4 d = dgs[r];
+                    float4* gp = dgeo + (size_t)i * KMAX + (r - a * NN);
+                    float4 acc4 = *gp;
+                    acc4.x += d.x + gv[0]; acc4.y += d.y + gv[1]; acc4.z += d.z + gv[2]; acc4.w += d.w;
+                    *gp = acc4;
+                }
+            }
             if (i >= N1 || i == 0 || j == 0) continue;
             const float4 g = sm.geo[r];
             const float pj[3] = {p_in[(size_t)j * 96 + s], p_in[(size_t)j * 96 + 32 + s], p_in[(size_t)j * 96 + 64 + s]};
@@ -904,22 +946,89 @@ __global__ __launch_bounds__(256) void k_layer_v1_bwd(const float* __restrict__ 
     }
 }
 
-void launch_layer_v1_bwd(hipStream_t st, const float* W, fx_t* G, const LayerW& lw, int N1, const int* ids_s, const float4* geo, const float* q_in,
-                         const float* p_in, const fx_t* dq_out, const fx_t* dp_out, fx_t* dq_in, fx_t* dp_in) {
+template <bool GEO>
+void launch_layer_v1_bwd_geo(hipStream_t st, const float* W, fx_t* G, const LayerW& lw, int N1, const int* ids_s, const float4* geo, const float* q_in,
+                             const float* p_in, const fx_t* dq_out, const fx_t* dp_out, fx_t* dq_in, fx_t* dp_in, float4* dgeo) {
     const int A = 64 / lw.nn;
     const dim3 grid((N1 + A - 1) / A), block(256);
     switch (lw.nn) {
-        case 8: hipLaunchKernelGGL(k_layer_v1_bwd<8>, grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in); break;
-        case 16: hipLaunchKernelGGL(k_layer_v1_bwd<16>, grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in); break;
-        case 32: hipLaunchKernelGGL(k_layer_v1_bwd<32>, grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in); break;
-        default: hipLaunchKernelGGL(k_layer_v1_bwd<64>, grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in); break;
+        case 8: hipLaunchKernelGGL((k_layer_v1_bwd<8, GEO>), grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in, dgeo); break;
+        case 16: hipLaunchKernelGGL((k_layer_v1_bwd<16, GEO>), grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in, dgeo); break;
+        case 32: hipLaunchKernelGGL((k_layer_v1_bwd<32, GEO>), grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in, dgeo); break;
+        default: hipLaunchKernelGGL((k_layer_v1_bwd<64, GEO>), grid, block, 0, st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in, dgeo); break;
     }
+}
+// dgeo == nullptr: parameter and state gradients only (the instantiation the training step runs)
+void launch_layer_v1_bwd(hipStream_t st, const float* W, fx_t* G, const LayerW& lw, int N1, const int* ids_s, const float4* geo, const float* q_in,
+                         const float* p_in, const fx_t* dq_out, const fx_t* dp_out, fx_t* dq_in, fx_t* dp_in, float4* dgeo = nullptr) {
+    if (dgeo) launch_layer_v1_bwd_geo<true>(st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in, dgeo);
+    else launch_layer_v1_bwd_geo<false>(st, W, G, lw, N1, ids_s, geo, q_in, p_in, dq_out, dp_out, dq_in, dp_in, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------- geometry backward
+// Backward of unpack_state_features (src/model_operations.py:8-14) from dgeo, one thread per (atom, slot). With r = X_j - X_i, D0 = |r|,
+// D = D0 + m [D0 < 1e-2], m = max D0 over the call and r^ = r / D:
+//   d D  = d d - (d r^ . r^) / D            (the distance column, and D as the divisor of r^)
+//   d r  = d r^ / D + d D r / D0            (d|r|/dr = 0 at r = 0, torch's convention)
+//   d m  = sum over the fix-up edges of d D (fixed-point atomic), handed to the maximal edges by k_unpack_bwd_max
+// +d r goes to X_j and -d r to X_i; j follows the forward's rule (a zero id is the call's last atom). r, D0 and the fix-up decision
+// come from pesto_geom.h, which restates k_unpack1 / k_unpack2 operation for operation, so the mask is the forward's. dX is 64-bit
+// fixed point: a repeated call gives the same bits.
+__global__ __launch_bounds__(256) void k_unpack_bwd(int N, const float* __restrict__ X, const int* __restrict__ ids_s, const float4* __restrict__ dgeo,
+                                                    const unsigned* __restrict__ dmax_bits, fx_t* __restrict__ dX, fx_t* __restrict__ dm,
+                                                    int* __restrict__ n_max) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)N * KMAX) return;      // (a wave = the 64 slots of one atom: it leaves as a whole)
+    const int i = (int)(e >> 6), c = (int)(e & 63);
+    const int id = ids_s[(size_t)(i + 1) * KMAX + c];
+    const int j = id > 0 ? id - 1 : N - 1;
+    float rx, ry, rz;
+    const float d0 = edge_vec(X + (size_t)3 * j, X + (size_t)3 * i, rx, ry, rz);
+    const unsigned mb = dmax_bits[0];
+    const bool fix = edge_fixup(d0);
+    const float D = edge_dist(d0, __uint_as_float(mb));
+    const float4 g = dgeo[(size_t)(i + 1) * KMAX + c];
+    const float dD = g.w - (g.x * (rx / D) + g.y * (ry / D) + g.z * (rz / D)) / D;
+    const float f = d0 > 0.0f ? dD / d0 : 0.0f;
+    float dr[3] = {g.x / D + f * rx, g.y / D + f * ry, g.z / D + f * rz};
+    if (fix) gadd(dm, dD);
+    if (d0 > 0.0f && __float_as_uint(d0) == mb) atomicAdd(n_max, 1);
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        gadd(dX + (size_t)3 * j + x, dr[x]);
+        float sum = dr[x];
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        if (c == 0) gadd(dX + (size_t)3 * i + x, -sum);
+    }
+}
+// m = max D0: d m is split evenly over the maximal edges (torch.max's backward). The fixtures contain one maximal edge or the two
+// directions of one pair, for which every split gives the same dX; other ties are not defined by the reference's gradient.
+__global__ __launch_bounds__(256) void k_unpack_bwd_max(int N, const float* __restrict__ X, const int* __restrict__ ids_s,
+                                                        const unsigned* __restrict__ dmax_bits, fx_t* __restrict__ dX, const fx_t* __restrict__ dm,
+                                                        const int* __restrict__ n_max) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)N * KMAX) return;
+    const int i = (int)(e >> 6), c = (int)(e & 63);
+    const int id = ids_s[(size_t)(i + 1) * KMAX + c];
+    const int j = id > 0 ? id - 1 : N - 1;
+    float rx, ry, rz;
+    const float d0 = edge_vec(X + (size_t)3 * j, X + (size_t)3 * i, rx, ry, rz);
+    if (!(d0 > 0.0f) || __float_as_uint(d0) != dmax_bits[0]) return;
+    const float f = from_fx(dm[0]) / (float)n_max[0] / d0;
+    const float dr[3] = {f * rx, f * ry, f * rz};
+#pragma unroll
+    for (int x = 0; x < 3; ++x) { gadd(dX + (size_t)3 * j + x, dr[x]); gadd(dX + (size_t)3 * i + x, -dr[x]); }
 }
 
 // ---------------------------------------------------------------------------------------------- blob order <-> image layout, Adam
 __global__ __launch_bounds__(256) void k_gather_grads(int64_t n, const int* __restrict__ map, const fx_t* __restrict__ Gimg, float* __restrict__ g) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) g[i] = from_fx(Gimg[map[i]]);
+}
+// the inverse direction: the plain section of the weight image from a blob (pesto_train_set_weights)
+__global__ __launch_bounds__(256) void k_scatter_weights(int64_t n, const int* __restrict__ map, const float* __restrict__ w, float* __restrict__ Wimg) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) Wimg[map[i]] = w[i];
 }
 __global__ __launch_bounds__(256) void k_to_fixed(int64_t n, const float* __restrict__ a, fx_t* __restrict__ b) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1007,9 +1116,20 @@ struct pesto_trainer {
     // per-call workspace
     DevBuf sq, sp, ids_s, geo, dmax, a_tmp, seg, z, dz, st, qh, ph, da, dqa, dpa, dqb, dpb, fq, fp;
     DevBuf in_X, in_ids, in_q0, in_roa, in_y, out_l, out_p;
+    DevBuf dgeo, dxf, gmax, out_dq0, out_dx;      // input gradients (pesto_train_backward)
+    // the kept forward a backward may follow (pesto_train_forward with keep != 0): valid == 0 means none. The pointers are the caller's
+    // device arrays or the handle's staging copies.
+    struct Kept {
+        int64_t valid = 0, N = 0, R = 0;
+        const float* X = nullptr;
+        const float* q0 = nullptr;
+        const int32_t* roa = nullptr;
+    } kept;
+    int64_t tickets = 0;
     void release() {
         for (DevBuf* b : {&W, &G, &blob, &am, &av, &gblob, &map, &pos, &flags, &sq, &sp, &ids_s, &geo, &dmax, &a_tmp, &seg, &z, &dz, &st, &qh, &ph,
-                          &da, &dqa, &dpa, &dqb, &dpb, &fq, &fp, &in_X, &in_ids, &in_q0, &in_roa, &in_y, &out_l, &out_p})
+                          &da, &dqa, &dpa, &dqb, &dpb, &fq, &fp, &in_X, &in_ids, &in_q0, &in_roa, &in_y, &out_l, &out_p, &dgeo, &dxf, &gmax,
+                          &out_dq0, &out_dx})
             b->release();
         for (hipEvent_t& e : ev)
             if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1099,6 +1219,118 @@ int stage_finish(pesto_trainer* t, hipStream_t st, float* grads_out) {
     return 0;
 }
 
+// ---- the pieces pesto_train_step, pesto_train_forward and pesto_train_backward share
+struct CallIn {
+    const float* X;
+    const void* ids;
+    const float* q0;
+    const int32_t* roa;
+};
+
+int check_call_args(int64_t N, int64_t R, int32_t k, int32_t ids_kind, const CallIn& in, int32_t ptr_kind) {
+    if (int rc = check_ptr_kind(ptr_kind)) return rc;
+    if (N < 1 || R < 1 || N > (1 << 24) || R > N || k < 1 || k > KMAX) return fail(PESTO_ERR_INVALID, "need 1 <= R <= N <= 2^24 and 1 <= k <= %d", KMAX);
+    if (ids_kind != PESTO_IDS_INT32 && ids_kind != PESTO_IDS_INT64) return fail(PESTO_ERR_INVALID, "ids_kind must be 32 or 64");
+    if (!in.X || !in.ids || !in.q0 || !in.roa) return fail(PESTO_ERR_INVALID, "null input");
+    return 0;
+}
+
+// host pointers: the inputs are copied to the handle's staging buffers, and `in` then names those
+int stage_inputs(pesto_trainer* t, hipStream_t st, int64_t N, int32_t k, int32_t ids_kind, CallIn& in) {
+    const int n0 = t->cfg.n0;
+    const size_t id_sz = ids_kind == PESTO_IDS_INT64 ? 8 : 4;
+    if (t->in_X.ensure((size_t)N * 12) || t->in_ids.ensure((size_t)N * k * id_sz) || t->in_q0.ensure((size_t)N * n0 * 4) || t->in_roa.ensure((size_t)N * 4))
+        return fail(PESTO_ERR_NOMEM, "staging allocation failed");
+    TRY_HIP(hipMemcpyAsync(t->in_X.p, in.X, (size_t)N * 12, hipMemcpyHostToDevice, st));
+    TRY_HIP(hipMemcpyAsync(t->in_ids.p, in.ids, (size_t)N * k * id_sz, hipMemcpyHostToDevice, st));
+    TRY_HIP(hipMemcpyAsync(t->in_q0.p, in.q0, (size_t)N * n0 * 4, hipMemcpyHostToDevice, st));
+    TRY_HIP(hipMemcpyAsync(t->in_roa.p, in.roa, (size_t)N * 4, hipMemcpyHostToDevice, st));
+    in.X = t->in_X.as<float>(); in.ids = t->in_ids.p; in.q0 = t->in_q0.as<float>(); in.roa = t->in_roa.as<int32_t>();
+    return 0;
+}
+
+// the argument check on the device, read back before anything else is launched; also finds the residue segments (t->seg)
+int check_on_device(pesto_trainer* t, hipStream_t st, int64_t N, int64_t R, int32_t k, int32_t ids_kind, const CallIn& in) {
+    int* lo = t->seg.as<int>();
+    int* hi = lo + R;
+    TRY_HIP(hipMemsetAsync(t->flags.p, 0, 256, st));
+    TRY_HIP(hipMemsetAsync(t->seg.p, 0, (size_t)R * 8, st));
+    const int64_t n = std::max<int64_t>(N * k, N);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (ids_kind == PESTO_IDS_INT64)
+        hipLaunchKernelGGL(k_train_check<long long>, grid, dim3(256), 0, st, (int)N, (int)R, k, (const long long*)in.ids, in.roa, lo, hi, err_ptr(t));
+    else
+        hipLaunchKernelGGL(k_train_check<int>, grid, dim3(256), 0, st, (int)N, (int)R, k, (const int*)in.ids, in.roa, lo, hi, err_ptr(t));
+    hipLaunchKernelGGL(k_train_check_empty, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, (int)R, hi, err_ptr(t));
+    int flag = 0;
+    TRY_HIP(hipMemcpyAsync(&flag, err_ptr(t), 4, hipMemcpyDeviceToHost, st));
+    TRY_HIP(hipStreamSynchronize(st));
+    if (flag & 1) return fail(PESTO_ERR_INVALID, "ids_topk holds an id outside [0, N]");
+    if (flag & 2) return fail(PESTO_ERR_INVALID, "res_of_atom holds a residue outside [0, R)");
+    if (flag & 4) return fail(PESTO_ERR_INVALID, "a residue has no atom");
+    return 0;
+}
+
+// state l of a kept forward is slot l; without keeping, the layers run on two ping-pong slots
+inline int state_slot(bool keep, int l) { return keep ? l : (l & 1); }
+
+// the training forward (k_embed, k_unpack*, k_layer_v1, pool): logits in t->z. keep: every layer's input state stays (L + 1 slots)
+int run_forward(pesto_trainer* t, hipStream_t st, int64_t N, int64_t R, int32_t k, int32_t ids_kind, const CallIn& in, bool keep) {
+    const int L = t->cfg.n_layers;
+    const size_t N1 = (size_t)N + 1;
+    float* sq = t->sq.as<float>();
+    float* sp = t->sp.as<float>();
+    const float* W = t->W.as<float>();
+    int* lo = t->seg.as<int>();
+    launch_embed(st, W, t->model.em, (int)N, (int)N, t->cfg.n0, in.q0, sq, sp);
+    // (the argument check has drained the stream, so the flags word may be cleared again for the geometry pass)
+    if (int rc = run_unpack(t, st, N, k, in.X, in.ids, ids_kind)) return rc;
+    for (int l = 0; l < L; ++l) {
+        const size_t a = (size_t)state_slot(keep, l), b = (size_t)state_slot(keep, l + 1);
+        launch_layer_v1(st, W, t->layers[l], (int)N1, t->ids_s.as<int>(), t->geo.as<float4>(), sq + a * N1 * S, sp + a * N1 * 96, sq + b * N1 * S,
+                        sp + b * N1 * 96);
+    }
+    const size_t last = (size_t)state_slot(keep, L);
+    launch_pool(st, W, t->model, t->cfg.n_out, (int)N, (int)R, sq + last * N1 * S + S, sp + last * N1 * 96 + 96, in.roa, t->a_tmp.as<float>(), lo, lo + R,
+                err_ptr(t), nullptr, nullptr, t->z.as<float>(), true);
+    return 0;
+}
+
+// the backward of a kept forward from t->dz: parameter gradients in t->gblob (blob order). dq0 (device, may be null) [N][n0];
+// want_dx: d X is left in t->dxf (fixed point, [N][3])
+int run_backward(pesto_trainer* t, hipStream_t st, int64_t N, int64_t R, const float* X, const float* q0, const int32_t* roa, float* dq0, bool want_dx) {
+    const int L = t->cfg.n_layers;
+    const size_t N1 = (size_t)N + 1;
+    const float* sq = t->sq.as<float>();
+    const float* sp = t->sp.as<float>();
+    const float* W = t->W.as<float>();
+    TRY_HIP(hipMemsetAsync(t->G.p, 0, t->img_floats * 8, st));
+    run_head_bwd(t, st, N, R, sq + (size_t)L * N1 * S + S, sp + (size_t)L * N1 * 96 + 96, roa);
+    float4* dgeo = want_dx ? t->dgeo.as<float4>() : nullptr;
+    if (want_dx) TRY_HIP(hipMemsetAsync(t->dgeo.p, 0, N1 * KMAX * 16, st));
+    fx_t *dqo = t->dqa.as<fx_t>(), *dpo = t->dpa.as<fx_t>(), *dqi = t->dqb.as<fx_t>(), *dpi = t->dpb.as<fx_t>();
+    for (int l = L - 1; l >= 0; --l) {
+        TRY_HIP(hipMemsetAsync(dqi, 0, N1 * S * 8, st));
+        TRY_HIP(hipMemsetAsync(dpi, 0, N1 * 96 * 8, st));
+        launch_layer_v1_bwd(st, W, t->G.as<fx_t>(), t->layers[l], (int)N1, t->ids_s.as<int>(), t->geo.as<float4>(), sq + (size_t)l * N1 * S,
+                            sp + (size_t)l * N1 * 96, dqo, dpo, dqi, dpi, dgeo);
+        std::swap(dqo, dqi); std::swap(dpo, dpi);
+    }
+    to_float(st, N1 * S, dqo, t->fq.as<float>());
+    hipLaunchKernelGGL(k_embed_bwd, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, W, t->G.as<fx_t>(), t->model.em, (int)N, t->cfg.n0, q0, t->fq.as<float>(),
+                       dq0);
+    if (want_dx) {
+        const dim3 grid((unsigned)(((size_t)N * KMAX + 255) / 256));
+        TRY_HIP(hipMemsetAsync(t->dxf.p, 0, (size_t)N * 3 * 8, st));
+        TRY_HIP(hipMemsetAsync(t->gmax.p, 0, 256, st));
+        fx_t* dm = t->gmax.as<fx_t>();
+        int* n_max = t->gmax.as<int>() + 4;
+        hipLaunchKernelGGL(k_unpack_bwd, grid, dim3(256), 0, st, (int)N, X, t->ids_s.as<int>(), dgeo, t->dmax.as<unsigned>(), t->dxf.as<fx_t>(), dm, n_max);
+        hipLaunchKernelGGL(k_unpack_bwd_max, grid, dim3(256), 0, st, (int)N, X, t->ids_s.as<int>(), t->dmax.as<unsigned>(), t->dxf.as<fx_t>(), dm, n_max);
+    }
+    return gather_grads(t, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1168,61 +1400,28 @@ int pesto_train_step(pesto_trainer* t, int32_t mode, int64_t N, int64_t R, int32
     if (int rc = check_trainer(t)) return rc;
     if (int rc = check_ptr_kind(ptr_kind)) return rc;
     if (mode < 0 || mode > 2) return fail(PESTO_ERR_INVALID, "mode must be 0 (eval_step), 1 (loss_and_grad) or 2 (train_step)");
-    if (N < 1 || R < 1 || N > (1 << 24) || R > N || k < 1 || k > KMAX) return fail(PESTO_ERR_INVALID, "need 1 <= R <= N <= 2^24 and 1 <= k <= %d", KMAX);
+    CallIn in{X, ids_topk, q0, res_of_atom};
+    if (int rc = check_call_args(N, R, k, ids_kind, in, ptr_kind)) return rc;
     if (C != t->cfg.n_out) return fail(PESTO_ERR_INVALID, "y has %d columns, the model has n_out = %d", C, t->cfg.n_out);
-    if (ids_kind != PESTO_IDS_INT32 && ids_kind != PESTO_IDS_INT64) return fail(PESTO_ERR_INVALID, "ids_kind must be 32 or 64");
-    if (!X || !ids_topk || !q0 || !res_of_atom || !y) return fail(PESTO_ERR_INVALID, "null input");
+    if (!y) return fail(PESTO_ERR_INVALID, "null input");
     const bool dev = ptr_kind == PESTO_PTR_DEVICE;
     hipStream_t st = dev ? (hipStream_t)stream : t->stream;
-    const int L = t->cfg.n_layers, n0 = t->cfg.n0;
-    const size_t N1 = (size_t)N + 1, id_sz = ids_kind == PESTO_IDS_INT64 ? 8 : 4, rc4 = (size_t)R * C * 4;
+    const int L = t->cfg.n_layers;
+    const size_t rc4 = (size_t)R * C * 4;
+    t->kept.valid = 0;      // the states of a kept forward are overwritten
     if (int rc = ensure_state(t, N, R, L + 1)) return rc;
     if (t->out_l.ensure(rc4) || t->out_p.ensure(rc4)) return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
     if (!dev) {
-        if (t->in_X.ensure((size_t)N * 12) || t->in_ids.ensure((size_t)N * k * id_sz) || t->in_q0.ensure((size_t)N * n0 * 4) || t->in_roa.ensure((size_t)N * 4) ||
-            t->in_y.ensure(rc4)) return fail(PESTO_ERR_NOMEM, "staging allocation failed");
-        TRY_HIP(hipMemcpyAsync(t->in_X.p, X, (size_t)N * 12, hipMemcpyHostToDevice, st));
-        TRY_HIP(hipMemcpyAsync(t->in_ids.p, ids_topk, (size_t)N * k * id_sz, hipMemcpyHostToDevice, st));
-        TRY_HIP(hipMemcpyAsync(t->in_q0.p, q0, (size_t)N * n0 * 4, hipMemcpyHostToDevice, st));
-        TRY_HIP(hipMemcpyAsync(t->in_roa.p, res_of_atom, (size_t)N * 4, hipMemcpyHostToDevice, st));
+        if (t->in_y.ensure(rc4)) return fail(PESTO_ERR_NOMEM, "staging allocation failed");
+        if (int rc = stage_inputs(t, st, N, k, ids_kind, in)) return rc;
         TRY_HIP(hipMemcpyAsync(t->in_y.p, y, rc4, hipMemcpyHostToDevice, st));
-        X = t->in_X.as<float>(); ids_topk = t->in_ids.p; q0 = t->in_q0.as<float>(); res_of_atom = t->in_roa.as<int32_t>(); y = t->in_y.as<float>();
+        y = t->in_y.as<float>();
     }
-    // ---- argument check on the device, read back before anything else is launched
-    int* lo = t->seg.as<int>();
-    int* hi = lo + R;
-    TRY_HIP(hipMemsetAsync(t->flags.p, 0, 256, st));
-    TRY_HIP(hipMemsetAsync(t->seg.p, 0, (size_t)R * 8, st));
-    {
-        const int64_t n = std::max<int64_t>(N * k, N);
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (ids_kind == PESTO_IDS_INT64)
-            hipLaunchKernelGGL(k_train_check<long long>, grid, dim3(256), 0, st, (int)N, (int)R, k, (const long long*)ids_topk, res_of_atom, lo, hi, err_ptr(t));
-        else
-            hipLaunchKernelGGL(k_train_check<int>, grid, dim3(256), 0, st, (int)N, (int)R, k, (const int*)ids_topk, res_of_atom, lo, hi, err_ptr(t));
-        hipLaunchKernelGGL(k_train_check_empty, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, (int)R, hi, err_ptr(t));
-        int flag = 0;
-        TRY_HIP(hipMemcpyAsync(&flag, err_ptr(t), 4, hipMemcpyDeviceToHost, st));
-        TRY_HIP(hipStreamSynchronize(st));
-        if (flag & 1) return fail(PESTO_ERR_INVALID, "ids_topk holds an id outside [0, N]");
-        if (flag & 2) return fail(PESTO_ERR_INVALID, "res_of_atom holds a residue outside [0, R)");
-        if (flag & 4) return fail(PESTO_ERR_INVALID, "a residue has no atom");
-    }
+    if (int rc = check_on_device(t, st, N, R, k, ids_kind, in)) return rc;
     if (mode == 2) t->global_step += 1;
-    float* sq = t->sq.as<float>();
-    float* sp = t->sp.as<float>();
-    const float* W = t->W.as<float>();
     if (t->timing) TRY_HIP(hipEventRecord(t->ev[0], st));
     // ---- training forward: every layer's input state is kept
-    launch_embed(st, W, t->model.em, (int)N, (int)N, n0, q0, sq, sp);
-    // (the argument check above has drained the stream, so the flags word may be cleared again for the geometry pass)
-    if (int rc = run_unpack(t, st, N, k, X, ids_topk, ids_kind)) return rc;
-    for (int l = 0; l < L; ++l)
-        launch_layer_v1(st, W, t->layers[l], (int)N1, t->ids_s.as<int>(), t->geo.as<float4>(), sq + (size_t)l * N1 * S, sp + (size_t)l * N1 * 96,
-                        sq + (size_t)(l + 1) * N1 * S, sp + (size_t)(l + 1) * N1 * 96);
-    const float* qL = sq + (size_t)L * N1 * S + S;
-    const float* pL = sp + (size_t)L * N1 * 96 + 96;
-    launch_pool(st, W, t->model, C, (int)N, (int)R, qL, pL, res_of_atom, t->a_tmp.as<float>(), lo, hi, err_ptr(t), nullptr, nullptr, t->z.as<float>(), true);
+    if (int rc = run_forward(t, st, N, R, k, ids_kind, in, true)) return rc;
     // ---- loss
     hipLaunchKernelGGL(k_pos_ratios, dim3(1), dim3(256), 0, st, (int)R, C, y, t->pos.as<float>(), (float)(1.0 + std::sqrt((double)t->global_step)));
     float* losses_d = dev && losses_out ? losses_out : t->out_l.as<float>();
@@ -1232,19 +1431,7 @@ int pesto_train_step(pesto_trainer* t, int32_t mode, int64_t N, int64_t R, int32
     if (t->timing) TRY_HIP(hipEventRecord(t->ev[1], st));
     if (mode) {
         // ---- backward
-        TRY_HIP(hipMemsetAsync(t->G.p, 0, t->img_floats * 8, st));
-        run_head_bwd(t, st, N, R, qL, pL, res_of_atom);
-        fx_t *dqo = t->dqa.as<fx_t>(), *dpo = t->dpa.as<fx_t>(), *dqi = t->dqb.as<fx_t>(), *dpi = t->dpb.as<fx_t>();
-        for (int l = L - 1; l >= 0; --l) {
-            TRY_HIP(hipMemsetAsync(dqi, 0, N1 * S * 8, st));
-            TRY_HIP(hipMemsetAsync(dpi, 0, N1 * 96 * 8, st));
-            launch_layer_v1_bwd(st, W, t->G.as<fx_t>(), t->layers[l], (int)N1, t->ids_s.as<int>(), t->geo.as<float4>(), sq + (size_t)l * N1 * S,
-                                sp + (size_t)l * N1 * 96, dqo, dpo, dqi, dpi);
-            std::swap(dqo, dqi); std::swap(dpo, dpi);
-        }
-        to_float(st, N1 * S, dqo, t->fq.as<float>());
-        hipLaunchKernelGGL(k_embed_bwd, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, W, t->G.as<fx_t>(), t->model.em, (int)N, n0, q0, t->fq.as<float>());
-        if (int rc = gather_grads(t, st)) return rc;
+        if (int rc = run_backward(t, st, N, R, in.X, in.q0, in.roa, nullptr, false)) return rc;
         if (t->timing) TRY_HIP(hipEventRecord(t->ev[2], st));
         if (mode == 2) {
             if (int rc = run_adam(t, st)) return rc;
@@ -1266,9 +1453,85 @@ int pesto_train_step(pesto_trainer* t, int32_t mode, int64_t N, int64_t R, int32
     return 0;
 }
 
+int pesto_train_set_weights(pesto_trainer* t, const float* blob, int32_t ptr_kind, void* stream) {
+    if (int rc = check_trainer(t)) return rc;
+    if (int rc = check_ptr_kind(ptr_kind)) return rc;
+    if (!blob) return fail(PESTO_ERR_INVALID, "null weight blob");
+    const bool dev = ptr_kind == PESTO_PTR_DEVICE;
+    hipStream_t st = dev ? (hipStream_t)stream : t->stream;
+    t->kept.valid = 0;      // a backward would recompute the kept forward from other weights
+    if (!dev) TRY_HIP(hipDeviceSynchronize());
+    TRY_HIP(hipMemcpyAsync(t->blob.p, blob, (size_t)t->n_weights * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_scatter_weights, dim3((unsigned)((t->n_weights + 255) / 256)), dim3(256), 0, st, t->n_weights, t->map.as<int>(),
+                       t->blob.as<float>(), t->W.as<float>());
+    TRY_HIP(hipGetLastError());
+    if (!dev) TRY_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int pesto_train_forward(pesto_trainer* t, int32_t keep, int64_t N, int64_t R, int32_t k, const float* X, const void* ids_topk, int32_t ids_kind,
+                        const float* q0, const int32_t* res_of_atom, float* z_out, int64_t* ticket_out, int32_t ptr_kind, void* stream) {
+    if (int rc = check_trainer(t)) return rc;
+    CallIn in{X, ids_topk, q0, res_of_atom};
+    if (int rc = check_call_args(N, R, k, ids_kind, in, ptr_kind)) return rc;
+    if (!z_out || (keep && !ticket_out)) return fail(PESTO_ERR_INVALID, "null output");
+    const bool dev = ptr_kind == PESTO_PTR_DEVICE;
+    hipStream_t st = dev ? (hipStream_t)stream : t->stream;
+    const size_t rc4 = (size_t)R * t->cfg.n_out * 4;
+    t->kept.valid = 0;      // every forward runs on the handle's one workspace: an earlier ticket ends here
+    if (int rc = ensure_state(t, N, R, keep ? t->cfg.n_layers + 1 : 2)) return rc;
+    if (!dev)
+        if (int rc = stage_inputs(t, st, N, k, ids_kind, in)) return rc;
+    if (int rc = check_on_device(t, st, N, R, k, ids_kind, in)) return rc;
+    if (int rc = run_forward(t, st, N, R, k, ids_kind, in, keep != 0)) return rc;
+    TRY_HIP(hipGetLastError());
+    TRY_HIP(hipMemcpyAsync(z_out, t->z.p, rc4, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    if (!dev) TRY_HIP(hipStreamSynchronize(st));
+    if (keep) {
+        t->kept.valid = ++t->tickets;
+        t->kept.N = N; t->kept.R = R; t->kept.X = in.X; t->kept.q0 = in.q0; t->kept.roa = in.roa;
+        *ticket_out = t->kept.valid;
+    }
+    return 0;
+}
+
+int pesto_train_backward(pesto_trainer* t, int64_t ticket, const float* dz, float* grads_out, float* dq0_out, float* dX_out, int32_t ptr_kind,
+                         void* stream) {
+    if (int rc = check_trainer(t)) return rc;
+    if (int rc = check_ptr_kind(ptr_kind)) return rc;
+    if (!dz) return fail(PESTO_ERR_INVALID, "null dz");
+    if (ticket < 1 || ticket != t->kept.valid)
+        return fail(PESTO_ERR_INVALID, "ticket %lld is not the handle's last kept forward: a later forward, training step, stage call or weight "
+                    "update has replaced its states (backward must follow its own forward)", (long long)ticket);
+    const bool dev = ptr_kind == PESTO_PTR_DEVICE;
+    hipStream_t st = dev ? (hipStream_t)stream : t->stream;
+    const int64_t N = t->kept.N, R = t->kept.R;
+    const int n0 = t->cfg.n0;
+    const size_t rc4 = (size_t)R * t->cfg.n_out * 4, N1 = (size_t)N + 1;
+    if (dX_out && (t->dgeo.ensure(N1 * KMAX * 16) || t->dxf.ensure((size_t)N * 3 * 8) || t->gmax.ensure(256) || t->out_dx.ensure((size_t)N * 12)))
+        return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
+    if (dq0_out && !dev && t->out_dq0.ensure((size_t)N * n0 * 4)) return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
+    TRY_HIP(hipMemcpyAsync(t->dz.p, dz, rc4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    float* dq0_d = !dq0_out ? nullptr : dev ? dq0_out : t->out_dq0.as<float>();
+    if (int rc = run_backward(t, st, N, R, t->kept.X, t->kept.q0, t->kept.roa, dq0_d, dX_out != nullptr)) return rc;
+    float* dx_d = dev ? dX_out : t->out_dx.as<float>();
+    if (dX_out) to_float(st, (size_t)N * 3, t->dxf.as<fx_t>(), dx_d);
+    TRY_HIP(hipGetLastError());
+    if (dev) {
+        if (grads_out) TRY_HIP(hipMemcpyAsync(grads_out, t->gblob.p, (size_t)t->n_weights * 4, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    if (grads_out) TRY_HIP(hipMemcpyAsync(grads_out, t->gblob.p, (size_t)t->n_weights * 4, hipMemcpyDeviceToHost, st));
+    if (dq0_out) TRY_HIP(hipMemcpyAsync(dq0_out, dq0_d, (size_t)N * n0 * 4, hipMemcpyDeviceToHost, st));
+    if (dX_out) TRY_HIP(hipMemcpyAsync(dX_out, dx_d, (size_t)N * 12, hipMemcpyDeviceToHost, st));
+    TRY_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 int pesto_train_adam(pesto_trainer* t, const float* grads) {
     if (int rc = check_trainer(t)) return rc;
     if (!grads) return fail(PESTO_ERR_INVALID, "null gradient");
+    t->kept.valid = 0;
     TRY_HIP(hipDeviceSynchronize());
     TRY_HIP(hipMemcpyAsync(t->gblob.p, grads, (size_t)t->n_weights * 4, hipMemcpyHostToDevice, t->stream));
     if (int rc = run_adam(t, t->stream)) return rc;
@@ -1320,6 +1583,7 @@ int pesto_train_get_timing(pesto_trainer* t, double* ms_out) {
 int pesto_train_stage_embed(pesto_trainer* t, int64_t N, const float* q0, const float* dq, float* grads_out) {
     if (int rc = check_trainer(t)) return rc;
     if (N < 1 || N > (1 << 24) || !q0 || !dq) return fail(PESTO_ERR_INVALID, "bad arguments");
+    t->kept.valid = 0;
     if (int rc = ensure_state(t, N, 1, 1)) return rc;
     const int n0 = t->cfg.n0;
     if (t->in_q0.ensure((size_t)N * n0 * 4)) return fail(PESTO_ERR_NOMEM, "staging allocation failed");
@@ -1329,7 +1593,7 @@ int pesto_train_stage_embed(pesto_trainer* t, int64_t N, const float* q0, const 
     TRY_HIP(hipMemcpyAsync(t->in_q0.p, q0, (size_t)N * n0 * 4, hipMemcpyHostToDevice, st));
     TRY_HIP(hipMemcpyAsync(t->fq.as<float>() + S, dq, (size_t)N * S * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_embed_bwd, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, t->W.as<float>(), t->G.as<fx_t>(), t->model.em, (int)N, n0,
-                       t->in_q0.as<float>(), t->fq.as<float>());
+                       t->in_q0.as<float>(), t->fq.as<float>(), (float*)nullptr);
     return stage_finish(t, st, grads_out);
 }
 
@@ -1340,6 +1604,7 @@ int pesto_train_stage_layer(pesto_trainer* t, int32_t layer, int64_t N, int32_t 
     if (layer < 0 || layer >= t->cfg.n_layers || N < 1 || N > (1 << 24) || k < 1 || k > KMAX || !X || !ids_topk || !q_in || !p_in || !dq_out || !dp_out)
         return fail(PESTO_ERR_INVALID, "bad arguments");
     if (ids_kind != PESTO_IDS_INT32 && ids_kind != PESTO_IDS_INT64) return fail(PESTO_ERR_INVALID, "ids_kind must be 32 or 64");
+    t->kept.valid = 0;
     if (int rc = ensure_state(t, N, 1, 1)) return rc;
     const size_t N1 = (size_t)N + 1, id_sz = ids_kind == PESTO_IDS_INT64 ? 8 : 4;
     if (t->in_X.ensure((size_t)N * 12) || t->in_ids.ensure((size_t)N * k * id_sz)) return fail(PESTO_ERR_NOMEM, "staging allocation failed");
@@ -1385,6 +1650,7 @@ int pesto_train_stage_head(pesto_trainer* t, int64_t N, int64_t R, const float* 
         for (int64_t r = 0; r < R; ++r)
             if (!seen[r]) return fail(PESTO_ERR_INVALID, "a residue has no atom");
     }
+    t->kept.valid = 0;
     if (int rc = ensure_state(t, N, R, 1)) return rc;
     if (t->in_roa.ensure((size_t)N * 4)) return fail(PESTO_ERR_NOMEM, "staging allocation failed");
     const int C = t->cfg.n_out;
