@@ -308,6 +308,57 @@ int pesto_interface_labels(pesto_model* m, int64_t n_total, int32_t n_struct, co
 int pesto_bc_scores(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const uint8_t* y, const float* p,
                     float* scores_out, int32_t ptr_kind, void* stream);
 
+/* ---- ranking curves and pooled scores (what the reference's evaluation notebooks take from sklearn.metrics) ----
+ * replaces: metrics.roc_curve, metrics.precision_recall_curve with metrics.auc, metrics.f1_score and the label-split confidence
+ * histograms of interface_ppi_benchmark.ipynb, interface_type_evaluation.ipynb, interface_ppi_confidence.ipynb and
+ * interfaceome/eukaryotic_protein_complexes_scoring_analysis.ipynb, on columns of 10^5 to 10^7 pooled residues.
+ * Failures of the entry points below are reported through pesto_rank_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the evaluation group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ *
+ * The inputs are pesto_bc_scores': y uint8 [R,n_class] (0 / non-zero), p float32 [R,n_class], res_offsets int32 [n_struct+1] (HOST, every
+ * segment >= 1 row), R * n_class <= 2^31 - 1, n_class <= 1024, n_struct * n_class <= PESTO_RANK_MAX_COLUMNS. A column is one (segment,
+ * class) pair, col = s * n_class + c; pooled evaluation is n_struct = 1. A non-finite p (NaN, +-inf) makes the call return PESTO_ERR_INVALID (a device flag read back with the
+ * outputs; sklearn refuses the same inputs). Every element becomes the key col << 33 | desc(p) << 1 | y (desc: the order-preserving map of
+ * the float's bits, complemented, -0.0 taken as +0.0) and all columns are sorted at once by one LSD radix sort of 8-bit digits; the
+ * distinct scores of a column in descending order are its thresholds, and with an integer scan of y the k-th has
+ *     tps[k] = positives with p >= thr[k]      fps[k] = negatives with p >= thr[k]           (sklearn's _binary_clf_curve)
+ * Everything below is exact integer arithmetic up to the final divisions, and bit-identical from call to call. */
+const char* pesto_rank_last_error(void);
+
+enum {
+    PESTO_RANK_TILE = 2048,                   /* keys one workgroup handles per radix pass */
+    PESTO_RANK_MAX_COLUMNS = (1 << 24) - 1    /* n_struct * n_class: a workgroup of 256 threads per column, below 2^32 threads per launch */
+};
+
+/* counts_out int64 [n_struct,6,n_class], rows P, N, TP, FP (q = round(p) half to even != 0, as pesto_bc_scores), K (distinct thresholds),
+ * K_roc (the points roc_curve keeps with drop_intermediate, see pesto_rank_curves). scores_out float64 [n_struct,3,n_class], rows
+ *     roc_auc = (double)u2 / (2.0 * P * N), u2 = sum_k (fps[k] - fps[k-1]) * (tps[k] + tps[k-1]) in uint64: the integer pesto_bc_scores
+ *               counts over all pairs, so its float32 rounding equals that function's auc row bit for bit; NaN unless P > 0 and N > 0
+ *     pr_auc  = the trapezoid of precision tps / (tps + fps) over recall tps / P on the points of precision_recall_curve including the
+ *               closing point (recall 0, precision 1) - metrics.auc(recall, precision) - summed in float64 in a fixed order; NaN when
+ *               P = 0 (sklearn then sets recall to 1 with a warning)
+ *     f1      = 2 TP / (2 TP + FP + FN), 0.0 when the denominator is 0 */
+int pesto_rank_scores(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const uint8_t* y, const float* p,
+                      int64_t* counts_out, double* scores_out, int32_t ptr_kind, void* stream);
+
+/* Column col owns the rows offsets_out[col] .. offsets_out[col+1] of thr_out float32 [capacity], tps_out int64 [capacity] and fps_out
+ * int64 [capacity], thresholds descending. mode 0: every distinct threshold - the points of precision_recall_curve and of
+ * roc_curve(drop_intermediate=False). mode 1: the first point, the last point and every point where the second difference of fps or of tps
+ * is not zero - roc_curve's drop_intermediate=True, applied as sklearn applies it, before the (0, 0) point is prepended; the curve is
+ * thinned on the device. offsets_out int64 [n_struct * n_class + 1]; sizes_out int64 [1] (HOST): K, the points of all columns. The capacity
+ * protocol of pesto_frame_contacts (0 <= capacity < 2^31; thr_out, tps_out and fps_out may be NULL for 0): complete when K <= capacity,
+ * otherwise only offsets_out and K are, nothing is emitted and the call must be repeated with the capacity K. */
+int pesto_rank_curves(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const uint8_t* y, const float* p,
+                      int32_t mode, int64_t capacity, int64_t* offsets_out, float* thr_out, int64_t* tps_out, int64_t* fps_out,
+                      int64_t* sizes_out, int32_t ptr_kind, void* stream);
+
+/* edges float32 [n_bins+1] (HOST), strictly increasing, no NaN; n_struct * n_class * n_bins < 2^31. counts_out int64
+ * [n_struct,n_class,n_bins,2]: counts_out[s,c,:,v] = np.histogram(p[y == v], bins=edges) of the column - left-closed bins, the last one closed
+ * on both sides - by binary search of every edge among the column's sorted thresholds. */
+int pesto_rank_histogram(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const uint8_t* y, const float* p,
+                         int32_t n_bins, const float* edges, int64_t* counts_out, int32_t ptr_kind, void* stream);
+
 /* ---- interface patches (no GPU counterpart in the reference) ----
  * Failures of the entry point below are reported through pesto_patches_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the evaluation group it uses the handle for its device, after

@@ -9,7 +9,8 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "interface_patches_batch", "residue_ca", "save_patches", "trajectory", "StatisticalContactsModel", "contacts_distribution", "contact_counts",
            "div_KL", "interface_ensemble_comparison", "residue_contact_maps", "native_contacts", "fnat", "superpose_transform", "superpose", "rmsd",
            "residue_centroids", "docking", "contacts", "frame_contacts", "frame_residue_contacts", "interface_atoms", "irmsd", "interface_rigid_docking", "hbonds", "frame_hbonds", "baker_hubbard",
-           "hydrogen_bonds", "unwrap_pbc", "atomic_masses", "hbond_tables", "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
+           "hydrogen_bonds", "unwrap_pbc", "atomic_masses", "hbond_tables", "ranking", "roc_curve", "precision_recall_curve", "confidence_histogram",
+           "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch or the built library
@@ -37,4 +38,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         hb = importlib.import_module(".hbonds", __name__)
         return hb if name == "hbonds" else getattr(hb, name)
+    if name in ("ranking", "roc_curve", "precision_recall_curve", "confidence_histogram"):
+        import importlib
+        rk = importlib.import_module(".ranking", __name__)
+        return rk if name == "ranking" else getattr(rk, name)
     raise AttributeError(name)
