@@ -359,6 +359,66 @@ int pesto_rank_curves(pesto_model* m, int32_t n_struct, const int32_t* res_offse
 int pesto_rank_histogram(pesto_model* m, int32_t n_struct, const int32_t* res_offsets, int32_t n_class, const uint8_t* y, const float* p,
                          int32_t n_bins, const float* edges, int64_t* counts_out, int32_t ptr_kind, void* stream);
 
+/* ---- surface-vertex benchmark scoring (masif-site_benchmark/masif_sppider_Intpred_comp.ipynb of the reference) ----
+ * replaces: pyflann's nearest atom of every mesh vertex, pymesh's vertex_area, and the Python dictionaries that carry labels from vertices
+ * to residues (is_res_iface, assign_labels_per_residue) and MaSIF's scores from vertices to residues (compute_pred_labels_per_residue).
+ * Failures of the entry points below are reported through pesto_surface_last_error() (thread-local message of the last failing call of this
+ * group; an invalid handle's message is copied there too). Like the evaluation group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ *
+ * A ragged batch of n_struct structures: v_offsets over V vertices, a_offsets over N atoms, r_offsets over R residues (int32 [n_struct+1],
+ * HOST, every structure >= 1 entry) and f_offsets over F faces (non-decreasing: a structure may have no face). Face indices and
+ * atom_residue are local to their structure; nearest-atom indices, and everything returned per vertex or per residue, are in batch order.
+ * No entry point uses a floating-point atomic: every sum is a 64-bit integer sum, every output the same bits from call to call. */
+const char* pesto_surface_last_error(void);
+
+enum {
+    PESTO_SURFACE_VERTEX_TILE = 256,          /* vertices one workgroup of the search owns */
+    PESTO_SURFACE_ATOM_TILE = 256,            /* atoms it holds in LDS at a time */
+    PESTO_SURFACE_SLAB = 512                  /* atoms of one structure one workgroup walks (slab = 0) */
+};
+
+/* vertices float32 [V,3], xyz float32 [N,3] -> index_out int32 [V] (batch atom index), distance_out float32 [V]. The key of a (vertex, atom)
+ * pair of one structure is the float32 squared distance fmaf(rz, rz, fmaf(ry, ry, rx * rx)) of the float32 differences; a key that is not
+ * finite (a NaN or infinite coordinate, an overflow) never matches; the smallest key wins, among equal keys the lowest atom index;
+ * distance = sqrtf(key). A vertex without a match gets -1 and NaN. This is EXACT, where the reference asks FLANN for an approximate
+ * neighbour in float64. slab: the atoms of one structure a workgroup walks, a multiple of PESTO_SURFACE_ATOM_TILE (0: PESTO_SURFACE_SLAB);
+ * the result does not depend on it. Two launches and one memset. */
+int pesto_surface_nearest(pesto_model* m, int32_t n_struct, const int32_t* v_offsets, const int32_t* a_offsets, const float* vertices,
+                          const float* xyz, int32_t slab, int32_t* index_out, float* distance_out, int32_t ptr_kind, void* stream);
+
+/* pymesh's vertex_area in fixed point: faces int32 [F,3] (local vertex indices) -> area_fixed_out int64 [V], the sum over the faces at a
+ * vertex of llrint(area / 3 * 2^40), area = 0.5 * sqrt(cx cx + cy cy + cz cz) of the cross product of the edge vectors (corner 1 - corner 0,
+ * corner 2 - corner 0) in float64 from the float32 coordinates, every operation rounded once as written and summed left to right. The
+ * area is area_fixed * 2^-40. PESTO_ERR_INVALID when a face index lies outside its structure (nothing is read there) or a face's third is
+ * not below 2^53 units (NaN included). One launch and two memsets. */
+int pesto_surface_areas(pesto_model* m, int32_t n_struct, const int32_t* v_offsets, const int32_t* f_offsets, const float* vertices,
+                        const int32_t* faces, int64_t* area_fixed_out, int32_t ptr_kind, void* stream);
+
+/* Per residue, over the vertices whose nearest atom (nearest int32 [V], batch index or -1: no residue) belongs to it (atom_residue int32
+ * [N], local): n_vertices_out int32 [R]; area_out and iface_area_out int64 [R], the sums of area_fixed int64 [V] over all of them and over
+ * those with iface uint8 [V] != 0; label_out uint8 [R] = ia > 5.0 && ia / a > 0.04 with ia, a the two sums * 2^-40 in float64 (the
+ * notebook's is_res_iface); max_score_out float32 [R], the maximum of vertex_score float32 [V] (both may be NULL), NaN for a residue
+ * without a vertex, -0.0 reported as +0.0. PESTO_ERR_INVALID for a non-finite vertex_score, an index of nearest outside its structure's
+ * atoms or an atom_residue outside its structure's residues. Two launches and up to five memsets. */
+int pesto_surface_residues(pesto_model* m, int32_t n_struct, const int32_t* v_offsets, const int32_t* a_offsets, const int32_t* r_offsets,
+                           const int32_t* nearest, const int32_t* atom_residue, const int64_t* area_fixed, const uint8_t* iface,
+                           const float* vertex_score, int32_t* n_vertices_out, int64_t* area_out, int64_t* iface_area_out, uint8_t* label_out,
+                           float* max_score_out, int32_t ptr_kind, void* stream);
+
+/* out float32 [n_vertices] = p_atom[nearest[v]], NaN where nearest[v] == -1 (PESTO_ERR_INVALID for any other index outside [0, n_atoms)).
+ * One launch. */
+int pesto_surface_vertex_scores(pesto_model* m, int64_t n_vertices, int64_t n_atoms, const int32_t* nearest, const float* p_atom, float* out,
+                                int32_t ptr_kind, void* stream);
+
+/* The residues with n_vertices int32 [R] > 0 and valid uint8 [R] != 0 (NULL: all valid), per structure in residue order: offsets_out int64
+ * [n_struct+1], residue_out int32 [capacity] (batch residue index), y_out uint8 [capacity] (label != 0), p_out float32 [capacity]
+ * (p_res float32 [R]); sizes_out int64 [1] (HOST): K. The capacity protocol of pesto_frame_contacts (capacity R always fits). A structure
+ * may come out empty. Three launches. */
+int pesto_surface_scored(pesto_model* m, int32_t n_struct, const int32_t* r_offsets, const int32_t* n_vertices, const uint8_t* label, const float* p_res,
+                         const uint8_t* valid, int64_t capacity, int64_t* offsets_out, int32_t* residue_out, uint8_t* y_out, float* p_out,
+                         int64_t* sizes_out, int32_t ptr_kind, void* stream);
+
 /* ---- interface patches (no GPU counterpart in the reference) ----
  * Failures of the entry point below are reported through pesto_patches_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the evaluation group it uses the handle for its device, after

@@ -10,6 +10,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "div_KL", "interface_ensemble_comparison", "residue_contact_maps", "native_contacts", "fnat", "superpose_transform", "superpose", "rmsd",
            "residue_centroids", "docking", "contacts", "frame_contacts", "frame_residue_contacts", "interface_atoms", "irmsd", "interface_rigid_docking", "hbonds", "frame_hbonds", "baker_hubbard",
            "hydrogen_bonds", "unwrap_pbc", "atomic_masses", "hbond_tables", "ranking", "roc_curve", "precision_recall_curve", "confidence_histogram",
+           "surface", "nearest_atoms", "vertex_areas", "residue_surface", "benchmark_surfaces", "read_ply", "write_ply",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
@@ -42,4 +43,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         rk = importlib.import_module(".ranking", __name__)
         return rk if name == "ranking" else getattr(rk, name)
+    if name in ("surface", "nearest_atoms", "vertex_areas", "residue_surface", "benchmark_surfaces", "read_ply", "write_ply"):
+        import importlib
+        sf = importlib.import_module(".surface", __name__)
+        return sf if name == "surface" else getattr(sf, name)
     raise AttributeError(name)

@@ -73,6 +73,8 @@ ABI_SYMBOLS = [
     "pesto_interface_atoms", "pesto_rigid_docking", "pesto_interface_rmsd", "pesto_hbonds_last_error", "pesto_frame_hbonds",
     "pesto_hbond_occupancy", "pesto_unwrap_pbc",
     "pesto_rank_last_error", "pesto_rank_scores", "pesto_rank_curves", "pesto_rank_histogram",
+    "pesto_surface_last_error", "pesto_surface_nearest", "pesto_surface_areas", "pesto_surface_residues", "pesto_surface_vertex_scores",
+    "pesto_surface_scored",
     "pesto_train_last_error", "pesto_train_create", "pesto_train_destroy", "pesto_train_step", "pesto_train_adam", "pesto_train_get_state",
     "pesto_train_set_state", "pesto_train_set_timing", "pesto_train_get_timing", "pesto_train_stage_embed", "pesto_train_stage_layer",
     "pesto_train_stage_head", "pesto_train_set_weights", "pesto_train_forward", "pesto_train_backward",
@@ -181,6 +183,13 @@ def load():
     lib.pesto_rank_scores.argtypes = [c_p, i32, c_p, i32, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_rank_curves.argtypes = [c_p, i32, c_p, i32, c_p, c_p, i32, i64, c_p, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_rank_histogram.argtypes = [c_p, i32, c_p, i32, c_p, c_p, i32, c_p, c_p, i32, c_p]
+    lib.pesto_surface_last_error.restype = ctypes.c_char_p
+    lib.pesto_surface_last_error.argtypes = []
+    lib.pesto_surface_nearest.argtypes = [c_p, i32, c_p, c_p, c_p, c_p, i32, c_p, c_p, i32, c_p]
+    lib.pesto_surface_areas.argtypes = [c_p, i32, c_p, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_surface_residues.argtypes = [c_p, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_surface_vertex_scores.argtypes = [c_p, i64, i64, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_surface_scored.argtypes = [c_p, i32, c_p, c_p, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_train_last_error.restype = ctypes.c_char_p
     lib.pesto_train_last_error.argtypes = []
     lib.pesto_train_create.argtypes = [P(PestoConfig), c_p, i64, ctypes.c_int, ctypes.c_float, ctypes.c_float, P(c_p)]
@@ -204,17 +213,17 @@ def load():
     for name in ABI_SYMBOLS:
         if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error",
                         "pesto_trajectory_last_error", "pesto_sasa_last_error", "pesto_dssp_last_error", "pesto_docking_last_error",
-                        "pesto_hbonds_last_error", "pesto_rank_last_error", "pesto_train_last_error"):
+                        "pesto_hbonds_last_error", "pesto_rank_last_error", "pesto_surface_last_error", "pesto_train_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are eleven channels:
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are twelve channels:
     pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
     pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error, pesto_docking_last_error,
-    pesto_hbonds_last_error, pesto_rank_last_error and pesto_train_last_error."""
+    pesto_hbonds_last_error, pesto_rank_last_error, pesto_surface_last_error and pesto_train_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")

@@ -1,4 +1,4 @@
-// pesto_call.h - the host plumbing of one analysis call (pesto_eval / patches / contacts / trajectory / sasa / dssp / rank .hip): the group's message
+// pesto_call.h - the host plumbing of one analysis call (pesto_eval / patches / contacts / trajectory / sasa / dssp / rank / surface .hip): the group's message
 // channel, the handle's synchronisation, the offsets check and the call's one stream-ordered allocation with its staged copies.
 //
 // Everything sits in an anonymous namespace, so every translation unit that includes this header keeps a message of its own

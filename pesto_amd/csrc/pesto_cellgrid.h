@@ -16,7 +16,8 @@
 // the count pass and in the payload they scatter beside the coordinates, both functors.
 // (pesto_sasa.hip includes this header for struct_of and block_scan_exclusive only: its grid is another one, in double and per frame;
 // pesto_dssp.hip likewise: it has no grid; pesto_docking.hip and pesto_hbonds.hip take the list protocol's scans, k_frame_scan and
-// k_list_offsets; pesto_rank.hip the one-workgroup scan and k_list_offsets.)
+// k_list_offsets; pesto_rank.hip the one-workgroup scan and k_list_offsets;
+// pesto_surface.hip struct_of and k_list_offsets.)
 #pragma once
 #include <hip/hip_runtime.h>
 
