@@ -709,18 +709,27 @@ __global__ __launch_bounds__(256) void k_layer_v1_bwd(const float* __restrict__ 
         sm.dl[(0 * 4 + apart) * 64 + ar] = dm[0];
         sm.dl[(1 * 4 + apart) * 64 + ar] = dm[1];
         __syncthreads();
-        // softmax: d logit = w (d w - sum w d w) / sdk
+        // softmax: d logit = w (d w - sum w d w) / sdk. The float32 weights sum to 1 + a few units in the last place, and the d logits of
+        // one softmax must sum to zero (the key biases' gradients are analytically zero): the mean is taken over the weights as they are,
+        // sum w d w / sum w, and subtracted in double, so what is left of that sum is rounding relative to |d w - mean| and not to
+        // |mean| (rows of equal edges - padding slots of a structure below k atoms - have d w = mean in every slot)
         float dlr[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            double dot = 0.0;
+            double dot = 0.0, wsum = 0.0;
             if (apart == 0) {
-                for (int c = 0; c < NN; ++c) dot += sm.lg[(h * 4) * 64 + ag0 + c] * sm.dl[(h * 4) * 64 + ag0 + c];
+                for (int c = 0; c < NN; ++c) {
+                    const double w = sm.lg[(h * 4) * 64 + ag0 + c];
+                    dot += w * sm.dl[(h * 4) * 64 + ag0 + c]; wsum += w;
+                }
             } else {
                 for (int pp = 1; pp < 4; ++pp)
-                    for (int c = 0; c < NN; ++c) dot += sm.lg[(h * 4 + pp) * 64 + ag0 + c] * sm.dl[(h * 4 + pp) * 64 + ag0 + c];
+                    for (int c = 0; c < NN; ++c) {
+                        const double w = sm.lg[(h * 4 + pp) * 64 + ag0 + c];
+                        dot += w * sm.dl[(h * 4 + pp) * 64 + ag0 + c]; wsum += w;
+                    }
             }
-            dlr[h] = sm.lg[(h * 4 + apart) * 64 + ar] * (dm[h] - (float)dot) / sdk;
+            dlr[h] = sm.lg[(h * 4 + apart) * 64 + ar] * (float)((double)dm[h] - dot / wsum) / sdk;
         }
         __syncthreads();
         sm.dl[(0 * 4 + apart) * 64 + ar] = dlr[0];
