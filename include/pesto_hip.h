@@ -557,6 +557,40 @@ int pesto_superpose(pesto_model* m, int64_t F, int64_t F_ref, int64_t N_ref, int
 int pesto_residue_centroids(pesto_model* m, int64_t F, int64_t N, int64_t R, const float* X_frames, const int32_t* perm, const int32_t* off,
                             float* out, int32_t ptr_kind, void* stream);
 
+/* ---- pairwise RMSD and frame clustering (the clustering step of md_analysis/apply_model_with_clustering.ipynb and
+ * clustering_analysis.ipynb; the notebooks' own clusterer is a third-party package that the reference does not contain) ----
+ * Failures of the entry points below are reported through pesto_cluster_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the trajectory group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`. Every
+ * output is bit-identical from call to call. */
+const char* pesto_cluster_last_error(void);
+
+enum {
+    PESTO_CLUSTER_MAX_PAIRS = 1 << 28,        /* Fa * Fb of pesto_pairwise_rmsd: the matrix is indexed in 32 bits */
+    PESTO_CLUSTER_MAX_FRAMES = 16384          /* F of pesto_gromos_clusters: F * F = PESTO_CLUSTER_MAX_PAIRS */
+};
+
+/* replaces: superpose_transform followed by the expression of rmsd (md_analysis/mdtraj_utils/trajectory_utils.py:190-207, 323), called
+ * once per pair of frames. xyz_a [Fa,N,3], xyz_b [Fb,N,3] or NULL (xyz_a against itself, Fb = Fa); sel int32 [n_sel] atom indices or NULL
+ * for all atoms (n_sel = N), used for the fit and for the measure; 1 <= n_sel <= N; Fa * Fb <= PESTO_CLUSTER_MAX_PAIRS.
+ *     D_out float32 [Fa,Fb]: scale * sqrt(mean over the selected atoms of |R (b_j - t_b) - (a_i - t_a)|^2) at the optimal proper rotation
+ *           (never a reflection), evaluated in double from the float32 coordinates as
+ *           sqrt(max((G_a + G_b - 2 (s0 + s1 + sign(det H) s2)) / n_sel, 0)), G the centred sums of squares and s the singular values of
+ *           the centred covariance H, rounded once.
+ * Without xyz_b only the pairs i <= j are evaluated and mirrored: D is bitwise symmetric with a diagonal of exactly 0, and off the
+ * diagonal it has the bits of the call with xyz_b = a copy of xyz_a. Device scratch: 16 bytes per frame and selected atom. */
+int pesto_pairwise_rmsd(pesto_model* m, int64_t Fa, int64_t Fb, int64_t N, int64_t n_sel, const float* xyz_a, const float* xyz_b, const int32_t* sel,
+                        double scale, float* D_out, int32_t ptr_kind, void* stream);
+
+/* replaces: the clustering of the frames in md_analysis/clustering_analysis.ipynb, by the GROMOS method (Daura et al. 1999) over a
+ * distance matrix. D float32 [F,F], 1 <= F <= PESTO_CLUSTER_MAX_FRAMES, bitwise symmetric (PESTO_ERR_INVALID otherwise; checked on the
+ * device); cutoff finite. adj[i,j] = D[i,j] <= cutoff or i == j (a NaN compares false). While a frame is active: the centre is the active
+ * frame with the most active neighbours (the lowest index on ties); it and its active neighbours get the next label and become inactive.
+ *     labels_out int32 [F]; centers_out, sizes_out int32 [F], of which the first *n_clusters_out are filled (sizes never increase);
+ *     n_clusters_out: one int32 in HOST memory. */
+int pesto_gromos_clusters(pesto_model* m, int64_t F, const float* D, float cutoff, int32_t* labels_out, int32_t* centers_out, int32_t* sizes_out,
+                          int32_t* n_clusters_out, int32_t ptr_kind, void* stream);
+
 /* ---- docking metrics and frame contacts (the remaining array functions of md_analysis/mdtraj_utils/trajectory_utils.py) ----
  * Failures of the entry points below are reported through pesto_docking_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the trajectory group they use the handle for its device, after

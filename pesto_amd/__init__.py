@@ -11,6 +11,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "residue_centroids", "docking", "contacts", "frame_contacts", "frame_residue_contacts", "interface_atoms", "irmsd", "interface_rigid_docking", "hbonds", "frame_hbonds", "baker_hubbard",
            "hydrogen_bonds", "unwrap_pbc", "atomic_masses", "hbond_tables", "ranking", "roc_curve", "precision_recall_curve", "confidence_histogram",
            "surface", "nearest_atoms", "vertex_areas", "residue_surface", "benchmark_surfaces", "read_ply", "write_ply",
+           "clustering", "pairwise_rmsd", "gromos_clusters", "cluster_frames",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
@@ -47,4 +48,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         sf = importlib.import_module(".surface", __name__)
         return sf if name == "surface" else getattr(sf, name)
+    if name in ("clustering", "pairwise_rmsd", "gromos_clusters", "cluster_frames"):
+        import importlib
+        cl = importlib.import_module(".clustering", __name__)
+        return cl if name == "clustering" else getattr(cl, name)
     raise AttributeError(name)

@@ -113,6 +113,43 @@ __device__ void kabsch_rotation(const double* H, double* R) {
 }
 
 
+// kabsch_rotation's sibling for a caller that needs the fit but not the rotation: s0 + s1 + sign(det H) s2 of the singular values
+// s0 >= s1 >= s2 of H, the trace of R^T H at the optimal proper rotation. The same one-sided Jacobi without V: the column norms of the
+// rotated H are the singular values. A rank-deficient H (coincident, collinear or planar atoms) has s2 = 0, so its sign does not matter;
+// the determinant is taken from H itself.
+__device__ double kabsch_trace(const double* H) {
+    double A[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) A[a][b] = H[3 * a + b];
+    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+                for (int k = 0; k < 3; ++k) { alpha += A[k][p] * A[k][p]; beta += A[k][q] * A[k][q]; gamma += A[k][p] * A[k][q]; }
+                if (fabs(gamma) <= 1e-15 * sqrt(alpha * beta)) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+                for (int k = 0; k < 3; ++k) {
+                    const double ap = A[k][p], aq = A[k][q];
+                    A[k][p] = c * ap - s * aq; A[k][q] = s * ap + c * aq;
+                }
+            }
+        if (!rotated) break;
+    }
+    double n[3];
+    for (int k = 0; k < 3; ++k) n[k] = sqrt(A[0][k] * A[0][k] + A[1][k] * A[1][k] + A[2][k] * A[2][k]);
+    if (n[0] < n[1]) { const double t = n[0]; n[0] = n[1]; n[1] = t; }
+    if (n[1] < n[2]) { const double t = n[1]; n[1] = n[2]; n[2] = t; }
+    if (n[0] < n[1]) { const double t = n[0]; n[0] = n[1]; n[1] = t; }
+    return det < 0.0 ? (n[0] + n[1]) - n[2] : (n[0] + n[1]) + n[2];
+}
+
+
 // ---- host side
 float from_bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
