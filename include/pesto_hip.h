@@ -591,6 +591,72 @@ int pesto_pairwise_rmsd(pesto_model* m, int64_t Fa, int64_t Fb, int64_t N, int64
 int pesto_gromos_clusters(pesto_model* m, int64_t F, const float* D, float cutoff, int32_t* labels_out, int32_t* centers_out, int32_t* sizes_out,
                           int32_t* n_clusters_out, int32_t ptr_kind, void* stream);
 
+/* ---- density-peak clustering of frames by the centre of their predicted interface (steps 3 to 5 of the clustering in
+ * md_analysis/apply_model_with_clustering.ipynb, cell lines 263-343, and clustering_analysis.ipynb) ----
+ * The notebooks hand the interface centres to CLoNe, a third-party package that the reference does not contain. CLoNe is NOT reproduced:
+ * what stands here is the published algorithm it derives from, density peaks (Rodriguez and Laio, Science 344, 2014). No equality with
+ * CLoNe's results is claimed.
+ * Failures of the entry points below are reported through pesto_peaks_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the cluster group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`. Every
+ * output is bit-identical from call to call; a refused call writes nothing.
+ *
+ * The distance source of the two clustering entry points is exactly one of
+ *     X float32 [F,d], 1 <= d <= PESTO_PEAKS_MAX_DIM, finite (PESTO_ERR_INVALID otherwise; checked on the device). The distance is
+ *       float32 without contraction, the dimensions added in ascending order: s = dx0*dx0; s = s + dx1*dx1; ...; dist = sqrt_rn(s), every
+ *       operation rounded to float32 (for d = 3 the trajectory group's squared distance and its root). Matrix-free: nothing of size
+ *       [n,n] is allocated; n <= PESTO_PEAKS_MAX_POINTS.
+ *     D float32 [F,F], F <= PESTO_CLUSTER_MAX_FRAMES, off the diagonal finite, >= 0 and bitwise symmetric (PESTO_ERR_INVALID otherwise;
+ *       checked on the device); the diagonal is ignored. d is ignored.
+ * idx int32 [n] selects rows (values in [0, F), else PESTO_ERR_INVALID) or is NULL (n = F); all indices below count the n selected rows. */
+const char* pesto_peaks_last_error(void);
+
+enum {
+    PESTO_PEAKS_MAX_POINTS = 1 << 17,         /* n over points: seven all-pairs passes of 8.6e9 pairs stay a matter of seconds */
+    PESTO_PEAKS_MAX_CLUSTERS = 1024,          /* n_clusters */
+    PESTO_PEAKS_MAX_DIM = 8,                  /* d: a staged point is 8 floats */
+    PESTO_PEAKS_MAX_FRAMES = 1 << 23          /* F of the interface centres: a workgroup per frame */
+};
+enum { PESTO_PEAKS_THRESHOLD = 0, PESTO_PEAKS_WEIGHTS = 1 };    /* mode of the interface centres */
+enum { PESTO_PEAKS_CUTOFF = 0, PESTO_PEAKS_GAUSSIAN = 1 };      /* kernel of the density */
+
+/* replaces: T = P > p_thr, Xc = sum_r(Xp T) / sum_r(T) and the interface radius r_int of apply_model_with_clustering.ipynb (cell lines
+ * 263-343), for every frame at once; the clusterer that follows there is CLoNe, which is not reproduced. Xp float32 [F,R,3]; PW float32
+ * [F,R]: the predictions P (PESTO_PEAKS_THRESHOLD: w_r = 1 where P > p_thr, a NaN compares false) or the weights themselves
+ * (PESTO_PEAKS_WEIGHTS: w_r = PW; a negative or non-finite one makes the call return PESTO_ERR_INVALID). Per frame, in double in a fixed
+ * order, terms of weight 0 skipped, each output rounded once:
+ *     wsum_out double [F] = S = sum w_r; centers_out float32 [F,3] = c = sum w_r x_r / S; rg_out float32 [F] = sqrt(sum w_r |x_r - c|^2 / S)
+ * A frame with S = 0 gets centers = rg = NaN. One workgroup per frame, two passes over its residues, no [F,R] intermediate. */
+int pesto_weighted_centers(pesto_model* m, int64_t F, int64_t R, const float* Xp, const float* PW, int32_t mode, float p_thr, float* centers_out,
+                           double* wsum_out, float* rg_out, int32_t ptr_kind, void* stream);
+
+/* replaces: the choice of d_c from the percentile pdc inside the notebooks' clusterer (clustering_analysis.ipynb; CLoNe itself is not
+ * reproduced). *dist_out (HOST memory): the k-th smallest (0-based) of the n (n - 1) / 2 distances over the pairs i < j of the selected
+ * rows, n >= 2, 0 <= k < n (n - 1) / 2. Exact: a radix select over the bit patterns of the non-negative float32 distances in three passes
+ * (digits of 11, 10 and 10 bits), each a histogram of integer counts (LDS bins per workgroup, 64-bit totals, integer atomics only); the
+ * distances are recomputed in every pass and never stored. */
+int pesto_pair_distance_rank(pesto_model* m, int64_t F, int32_t d, const float* X, const float* D, int64_t n, const int32_t* idx, int64_t k,
+                             float* dist_out, int32_t ptr_kind, void* stream);
+
+/* replaces: the clustering of the interface centres in apply_model_with_clustering.ipynb (cell lines 263-343) and
+ * clustering_analysis.ipynb, by density peaks; CLoNe, the notebooks' clusterer, is not reproduced. dc finite and > 0. "Denser" is the total
+ * order key(j) > key(i): rho_j > rho_i, or rho_j == rho_i and j < i.
+ *     rho_out double [n]: PESTO_PEAKS_CUTOFF the number of j != i with d_ij < dc (strictly); PESTO_PEAKS_GAUSSIAN sum over j != i of
+ *         exp(-(d_ij / dc)^2) in double from the float32 d_ij and dc, in a fixed order
+ *     nh_out int32 [n], delta_out float32 [n]: the denser j with the smallest d_ij (the lowest j among equal distances) and that distance;
+ *         for the densest point -1 and the largest d_ij (0 when n = 1)
+ *     centres: the densest point always. n_clusters = K in 1 .. min(n, PESTO_PEAKS_MAX_CLUSTERS): it and the K - 1 others with the largest
+ *         gamma_i = rho_i * (double)delta_i (the lower index first among equal ones). n_clusters = 0: it and every point with
+ *         rho_i >= rho_min and delta_i >= delta_min. centers_out, sizes_out int32 [n], of which the first *n_clusters_out are filled: the
+ *         centres from the densest to the least dense by key, and the members of each; n_clusters_out: one int32 in HOST memory
+ *     labels_out int32 [n]: labels[centers[c]] = c, labels[i] = labels[nh[i]] otherwise (pointer jumping, at most ceil(log2 n) rounds)
+ *     halo_out uint8 [n]: rho_i < rho_b[labels[i]], rho_b[c] the largest (rho_i + rho_j) / 2 over the pairs i in c, j not in c with
+ *         d_ij < dc (0 without such a pair), taken by an integer atomic maximum on the bits of the non-negative double
+ * All-pairs passes: density, nearest denser point, border density over the distances; two rankings without distances. */
+int pesto_density_peaks(pesto_model* m, int64_t F, int32_t d, const float* X, const float* D, int64_t n, const int32_t* idx, float dc, int32_t kernel,
+                        int32_t n_clusters, double rho_min, float delta_min, double* rho_out, float* delta_out, int32_t* nh_out, int32_t* labels_out,
+                        uint8_t* halo_out, int32_t* centers_out, int32_t* sizes_out, int32_t* n_clusters_out, int32_t ptr_kind, void* stream);
+
 /* ---- docking metrics and frame contacts (the remaining array functions of md_analysis/mdtraj_utils/trajectory_utils.py) ----
  * Failures of the entry points below are reported through pesto_docking_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the trajectory group they use the handle for its device, after

@@ -12,6 +12,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "hydrogen_bonds", "unwrap_pbc", "atomic_masses", "hbond_tables", "ranking", "roc_curve", "precision_recall_curve", "confidence_histogram",
            "surface", "nearest_atoms", "vertex_areas", "residue_surface", "benchmark_surfaces", "read_ply", "write_ply",
            "clustering", "pairwise_rmsd", "gromos_clusters", "cluster_frames",
+           "peaks", "interface_centers", "weighted_centers", "distance_quantile", "density_peaks", "cluster_interface_frames",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
@@ -52,4 +53,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         cl = importlib.import_module(".clustering", __name__)
         return cl if name == "clustering" else getattr(cl, name)
+    if name in ("peaks", "interface_centers", "weighted_centers", "distance_quantile", "density_peaks", "cluster_interface_frames"):
+        import importlib
+        pk = importlib.import_module(".peaks", __name__)
+        return pk if name == "peaks" else getattr(pk, name)
     raise AttributeError(name)

@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "pesto_interface_atoms", "pesto_rigid_docking", "pesto_interface_rmsd", "pesto_hbonds_last_error", "pesto_frame_hbonds",
     "pesto_hbond_occupancy", "pesto_unwrap_pbc",
     "pesto_cluster_last_error", "pesto_pairwise_rmsd", "pesto_gromos_clusters",
+    "pesto_peaks_last_error", "pesto_weighted_centers", "pesto_pair_distance_rank", "pesto_density_peaks",
     "pesto_rank_last_error", "pesto_rank_scores", "pesto_rank_curves", "pesto_rank_histogram",
     "pesto_surface_last_error", "pesto_surface_nearest", "pesto_surface_areas", "pesto_surface_residues", "pesto_surface_vertex_scores",
     "pesto_surface_scored",
@@ -183,6 +184,12 @@ def load():
     lib.pesto_cluster_last_error.argtypes = []
     lib.pesto_pairwise_rmsd.argtypes = [c_p, i64, i64, i64, i64, c_p, c_p, c_p, ctypes.c_double, c_p, i32, c_p]
     lib.pesto_gromos_clusters.argtypes = [c_p, i64, c_p, ctypes.c_float, c_p, c_p, c_p, P(i32), i32, c_p]
+    lib.pesto_peaks_last_error.restype = ctypes.c_char_p
+    lib.pesto_peaks_last_error.argtypes = []
+    lib.pesto_weighted_centers.argtypes = [c_p, i64, i64, c_p, c_p, i32, ctypes.c_float, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_pair_distance_rank.argtypes = [c_p, i64, i32, c_p, c_p, i64, c_p, i64, P(ctypes.c_float), i32, c_p]
+    lib.pesto_density_peaks.argtypes = [c_p, i64, i32, c_p, c_p, i64, c_p, ctypes.c_float, i32, i32, ctypes.c_double, ctypes.c_float,
+                                        c_p, c_p, c_p, c_p, c_p, c_p, c_p, P(i32), i32, c_p]
     lib.pesto_rank_last_error.restype = ctypes.c_char_p
     lib.pesto_rank_last_error.argtypes = []
     lib.pesto_rank_scores.argtypes = [c_p, i32, c_p, i32, c_p, c_p, c_p, c_p, i32, c_p]
@@ -218,7 +225,7 @@ def load():
     for name in ABI_SYMBOLS:
         if name not in ("pesto_last_error", "pesto_eval_last_error", "pesto_patches_last_error", "pesto_contacts_last_error",
                         "pesto_trajectory_last_error", "pesto_sasa_last_error", "pesto_dssp_last_error", "pesto_docking_last_error",
-                        "pesto_hbonds_last_error", "pesto_cluster_last_error", "pesto_rank_last_error", "pesto_surface_last_error",
+                        "pesto_hbonds_last_error", "pesto_cluster_last_error", "pesto_peaks_last_error", "pesto_rank_last_error", "pesto_surface_last_error",
                         "pesto_train_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
@@ -226,10 +233,10 @@ def load():
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are thirteen channels:
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are fourteen channels:
     pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
     pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error, pesto_docking_last_error,
-    pesto_hbonds_last_error, pesto_cluster_last_error, pesto_rank_last_error, pesto_surface_last_error and pesto_train_last_error."""
+    pesto_hbonds_last_error, pesto_cluster_last_error, pesto_peaks_last_error, pesto_rank_last_error, pesto_surface_last_error and pesto_train_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")
