@@ -727,6 +727,53 @@ int pesto_rigid_docking(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, con
 int pesto_interface_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_sel,
                          const int32_t* sel, double scale, float* rmsd_out, int32_t ptr_kind, void* stream);
 
+/* ---- DockQ scoring of docking decoys against the bound complex (fnat, interface RMSD, ligand RMSD, DockQ, CAPRI class) ----
+ * Failures of the entry points below are reported through pesto_dockq_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`. The
+ * distance and its tests are the docking group's; the RMSDs are evaluated in double from the float32 inputs and rounded once. No
+ * floating-point atomics: every output is bit-identical from call to call. Every index is checked on the device before anything
+ * dereferences it; a refused call returns PESTO_ERR_INVALID and writes nothing. */
+const char* pesto_dockq_last_error(void);
+
+enum {
+    PESTO_DOCKQ_MAX_FRAMES = 1 << 23,         /* a workgroup of 256 threads per decoy, below 2^32 threads per launch */
+    PESTO_DOCKQ_MAX_PAIRS = 1 << 24           /* native residue pairs of one call; each at most 2^31 - 1 atom pairs */
+};
+
+/* replaces, for F decoys of one complex at once: fnat through trajectory_utils.py's all-pairs residue maps of every frame (this
+ * library's pesto_residue_contact_maps over the full sides and pesto_native_contacts), irmsd (trajectory_utils.py:328-338) once the
+ * interface atoms are known, and what neither had: the ligand RMSD (a fit on one selection measured on another), the DockQ score (Basu and
+ * Wallner 2016) and the CAPRI class. xyz_ref float32 [N,3]: the bound complex; xyz float32 [F,N,3]: the decoys, same atom order.
+ *     pairs int32 [P,4], 1 <= P <= PESTO_DOCKQ_MAX_PAIRS: per native residue pair the ranges [a0, a1) and [b0, b1) of
+ *         perm int32 [n_perm] that hold the atoms of its receptor residue and of its ligand residue (atom indices in [0, N); ranges
+ *         non-empty, within [0, n_perm], (a1 - a0) (b1 - b0) < 2^31)
+ *     sel_I int32 [n_I >= 3]: the interface's backbone atoms; sel_R int32 [n_R >= 3]: the receptor's; sel_L int32 [n_L >= 1]: the ligand's
+ *     r_contact float32, scale > 0 (rounded to float32 for the distance test d < r_contact, used as given for the RMSDs)
+ * Per decoy f:
+ *     preserved_out int32 [F]: the pairs with an atom pair d < r_contact (a NaN distance passes no test)
+ *     fnat_out float32 [F] = float32(double(preserved) / double(P))
+ *     irmsd_out float32 [F]: the rmsd_out of pesto_interface_rmsd on sel_I, bit for bit
+ *     lrmsd_out float32 [F] = float32(sqrt(sum over sel_L of |x' - y|^2 / n_L) scale), x' the atom moved by the fit of the decoy onto
+ *         xyz_ref on sel_R (the first fit of pesto_rigid_docking, its identity short cut included: a decoy that is the reference gives 0)
+ *     dockq_out float32 [F] = float32((fnat + 1 / (1 + (irmsd / 1.5)^2) + 1 / (1 + (lrmsd / 8.5)^2)) / 3), in double from the three float32
+ *         values, every operation rounded as written
+ *     capri_out uint8 [F]: 3 if 2 preserved >= P and (lrmsd <= 1 or irmsd <= 1); else 2 if 10 preserved >= 3 P and (lrmsd <= 5 or
+ *         irmsd <= 2); else 1 if 10 preserved >= P and (lrmsd <= 10 or irmsd <= 4); else 0 - the fnat conditions on the integers
+ * One launch behind the index check, one workgroup per decoy: a wave per native pair with an early exit at its first contact, then the
+ * two fits. */
+int pesto_dockq(pesto_model* m, int64_t F, int64_t N, const float* xyz_ref, const float* xyz, int64_t P, const int32_t* pairs, int64_t n_perm,
+                const int32_t* perm, int64_t n_I, const int32_t* sel_I, int64_t n_R, const int32_t* sel_R, int64_t n_L, const int32_t* sel_L,
+                float r_contact, double scale, float* fnat_out, int32_t* preserved_out, float* irmsd_out, float* lrmsd_out, float* dockq_out,
+                uint8_t* capri_out, int32_t ptr_kind, void* stream);
+
+/* replaces: the rmsd expression of trajectory_utils.py:328-338 behind a superposition on OTHER atoms than it measures, which neither the
+ * reference's irmsd nor pesto_superpose offers (both fit and measure on one selection). xyz_ref [F_ref,N,3], F_ref = 1 or F; xyz [F,N,3];
+ * sel_fit int32 [n_fit >= 3], sel_measure int32 [n_measure >= 1], in [0, N). rmsd_out float32 [F] = float32(sqrt(sum over sel_measure of
+ * |x' - y|^2 / n_measure) scale), x' moved by the fit on sel_fit as in pesto_dockq, whose lrmsd_out this gives bit for bit for sel_R, sel_L. */
+int pesto_fit_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_fit, const int32_t* sel_fit,
+                   int64_t n_measure, const int32_t* sel_measure, double scale, float* rmsd_out, int32_t ptr_kind, void* stream);
+
 /* ---- hydrogen bonds and periodic unwrapping (hydrogen_bonds and unwrap_pbc of md_analysis/mdtraj_utils/trajectory_utils.py) ----
  * Failures of the entry points below are reported through pesto_hbonds_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after

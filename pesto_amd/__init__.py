@@ -13,6 +13,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "surface", "nearest_atoms", "vertex_areas", "residue_surface", "benchmark_surfaces", "read_ply", "write_ply",
            "clustering", "pairwise_rmsd", "gromos_clusters", "cluster_frames",
            "peaks", "interface_centers", "weighted_centers", "distance_quantile", "density_peaks", "cluster_interface_frames",
+           "dockq", "lrmsd", "fit_rmsd", "native_pairs", "capri_class",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
@@ -57,4 +58,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         pk = importlib.import_module(".peaks", __name__)
         return pk if name == "peaks" else getattr(pk, name)
+    if name in ("dockq", "lrmsd", "fit_rmsd", "native_pairs", "capri_class"):          # (dockq: the module; its function is dockq.dockq)
+        import importlib
+        dq = importlib.import_module(".dockq", __name__)
+        return dq if name == "dockq" else getattr(dq, name)
     raise AttributeError(name)
