@@ -774,6 +774,67 @@ int pesto_dockq(pesto_model* m, int64_t F, int64_t N, const float* xyz_ref, cons
 int pesto_fit_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_fit, const int32_t* sel_fit,
                    int64_t n_measure, const int32_t* sel_measure, double scale, float* rmsd_out, int32_t ptr_kind, void* stream);
 
+/* ---- lDDT model-quality scoring (Mariani et al. 2013): superposition-free, per residue, over all frames ----
+ * Failures of the entry points below are reported through pesto_lddt_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ *
+ * Definition (this library's own; no equality with OpenStructure's lddt is claimed: there is no stereochemistry filter, no renaming of
+ * symmetric side-chain atoms, no sequence separation and no periodic image). The distance is the docking group's,
+ * d(a, b) = fl32(sqrt_rn((dx*dx + dy*dy) + dz*dz)) * fl32(scale), and a NaN distance passes no test.
+ *     reference pairs: the ordered pairs (i, j), i != j, of atoms of one structure, both selected (sel uint8 [N], NULL: all), with
+ *         res_of_atom[i] != res_of_atom[j], d_ref(i, j) < r_incl in xyz_ref and, for mode 1 (inter), chain_of_atom[i] != chain_of_atom[j],
+ *         for mode 2 (intra) the chains equal (mode 0, all: chain_of_atom may be NULL). K of them; an atom with a non-finite reference
+ *         coordinate has none.
+ *     total[r] int32: the pairs with i in residue r
+ *     preserved[f,r,k] int32: those with fabsf(d_f(i, j) - d_ref(i, j)) < thresholds[k], the subtraction rounded once in float32
+ *     residue[f,r] float32 = float32(double(sum_k preserved[f,r,k]) / double(T total[r])), NaN where total[r] = 0
+ *     score[f,s] float32: the same quotient over the int64 sums over the residues of structure s, NaN for a structure without pairs
+ * Every output is an integer count or one rounded quotient of integers: bit-identical from call to call. */
+const char* pesto_lddt_last_error(void);
+
+enum {
+    PESTO_LDDT_MAX_FRAMES = 1 << 23,          /* frames of one call */
+    PESTO_LDDT_MAX_ENTRIES = 1 << 30,         /* reference pairs (list entries) of one call */
+    PESTO_LDDT_MAX_THRESHOLDS = 8
+};
+
+/* The reference list as CSR over the atoms: offsets_out int64 [N + 1], row i = offsets_out[i] .. offsets_out[i + 1] holds j_out int32 and
+ * d_out float32 = d_ref(i, j) of atom i's pairs, in no particular order within a row (the cell grid's). xyz_ref float32 [N,3] holds
+ * n_struct structures back to back (struct_offsets int32 [n_struct + 1], host memory; pairs never cross structures); res_of_atom int32
+ * [N]: labels that are only compared, any value >= 0 (a negative one: PESTO_ERR_INVALID, found on the device); chain_of_atom int32 [N]
+ * or NULL (mode 0); sel uint8 [N] or NULL; r_incl and scale positive and finite, rounded to float32.
+ * *n_pairs_out (host memory) = K is written whenever the count pass ran; the offsets on success; the K entries only when K <= capacity
+ * (capacity 0 with j_out = d_out = NULL asks for the count alone). K > PESTO_LDDT_MAX_ENTRIES: PESTO_ERR_INVALID, and nothing but
+ * *n_pairs_out is written. The grid of pesto_interface_labels at r_incl /
+ * scale, a count pass, a 64-bit scan and a fill pass; one synchronisation to read K. */
+int pesto_lddt_pairs(pesto_model* m, int64_t N, int32_t n_struct, const int32_t* struct_offsets, const float* xyz_ref, const int32_t* res_of_atom,
+                     const int32_t* chain_of_atom, const uint8_t* sel, int32_t mode, float r_incl, double scale, int64_t capacity,
+                     int64_t* offsets_out, int32_t* j_out, float* d_out, int64_t* n_pairs_out, int32_t ptr_kind, void* stream);
+
+/* lDDT of the F frames xyz float32 [F,N,3] against xyz_ref float32 [N,3] (same atom order; a missing atom has NaN coordinates).
+ *     struct_offsets, res_struct_offsets int32 [n_struct + 1], host memory: the atoms and the residue rows of every structure (a ragged
+ *         batch; one structure: {0, N} and {0, R})
+ *     res_of_atom int32 [N] in [0, R); perm int32 [N]: the atoms ordered by residue row; res_offsets int32 [R + 1]: row r owns
+ *         perm[res_offsets[r] .. res_offsets[r + 1]) (the atoms of a residue need not be adjacent)
+ *     thresholds float32 [T], host memory, 1 <= T <= PESTO_LDDT_MAX_THRESHOLDS, positive and ascending
+ *     offsets_in / j_in / d_in / K_in: the list of pesto_lddt_pairs, or offsets_in NULL: the list is built here from xyz_ref,
+ *         chain_of_atom, sel, mode and r_incl (which are not read when a list is given), sized after its count pass and freed on return
+ * Outputs: score_out float32 [F,n_struct], residue_out float32 [F,R], preserved_out int32 [F,R,T], total_out int32 [R] and n_pairs_out
+ * int64 [n_struct] (host memory). Every index is checked for what the kernels dereference by it - res_of_atom in [0, R), res_offsets an
+ * ordered split of [0, N], perm in [0, N) with each entry's atom in the residue whose range holds the entry, a residue's atoms inside its
+ * structure, a given list's offsets ascending from 0 to K and its partners in [0, N) - by a kernel whose verdict is read before anything
+ * else is launched: a refused call returns PESTO_ERR_INVALID and writes nothing. Not checked, because nothing is addressed by it: that
+ * perm names every atom once (a repeated atom counts twice) and that a given list's partners lie in their atom's structure (the list of
+ * pesto_lddt_pairs does). A list built here with K > PESTO_LDDT_MAX_ENTRIES: PESTO_ERR_INVALID with n_pairs_out[0] = K, nothing else
+ * written. Then the list (unless given), one scoring launch over all frames - a wave per (frame, residue), its lanes across
+ * a row's entries, integer counts in registers, no atomics - and one workgroup per (structure, frame) for the quotients. */
+int pesto_lddt(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int32_t* struct_offsets, const int32_t* res_struct_offsets,
+               const float* xyz_ref, const float* xyz, int64_t R, const int32_t* res_of_atom, const int32_t* perm, const int32_t* res_offsets,
+               const int32_t* chain_of_atom, const uint8_t* sel, int32_t mode, int32_t T, const float* thresholds, float r_incl, double scale,
+               int64_t K_in, const int64_t* offsets_in, const int32_t* j_in, const float* d_in, float* score_out,
+               float* residue_out, int32_t* preserved_out, int32_t* total_out, int64_t* n_pairs_out, int32_t ptr_kind, void* stream);
+
 /* ---- hydrogen bonds and periodic unwrapping (hydrogen_bonds and unwrap_pbc of md_analysis/mdtraj_utils/trajectory_utils.py) ----
  * Failures of the entry points below are reported through pesto_hbonds_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after

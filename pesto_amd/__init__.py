@@ -14,6 +14,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "clustering", "pairwise_rmsd", "gromos_clusters", "cluster_frames",
            "peaks", "interface_centers", "weighted_centers", "distance_quantile", "density_peaks", "cluster_interface_frames",
            "dockq", "lrmsd", "fit_rmsd", "native_pairs", "capri_class",
+           "lddt", "ilddt", "lddt_ca", "reference_pairs", "structure_lddt",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
@@ -62,4 +63,8 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         dq = importlib.import_module(".dockq", __name__)
         return dq if name == "dockq" else getattr(dq, name)
+    if name in ("lddt", "ilddt", "lddt_ca", "reference_pairs", "structure_lddt"):      # (lddt: the module; its function is lddt.lddt)
+        import importlib
+        ld = importlib.import_module(".lddt", __name__)
+        return ld if name == "lddt" else getattr(ld, name)
     raise AttributeError(name)
