@@ -60,8 +60,10 @@ def round_away(t):
     return -r if t < 0 else r
 
 
-def dssp(X, table, pro, chain, scale=1.0, flags=None):
-    """(codes uint8 [R], partners int32 [R, 4], energies int32 [R, 4]) of ONE structure, one frame. X float32 [n_atoms, 3]."""
+def dssp(X, table, pro, chain, scale=1.0, flags=None, detail=None):
+    """(codes uint8 [R], partners int32 [R, 4], energies int32 [R, 4]) of ONE structure, one frame. X float32 [n_atoms, 3].
+    flags (a list) receives every near-threshold decision; detail (a dict) the intermediates: 'bridges' {(i, j): 'P' | 'A'}, 'ladders'
+    [type, i_begin, i_end, j_begin, j_end, n] and 'roots', the index of the ladder that names each ladder's bulge-linked component."""
     R = len(table)
     flags = [] if flags is None else flags
 
@@ -231,6 +233,8 @@ def dssp(X, table, pro, chain, scale=1.0, flags=None):
     for r in range(R):
         if not full[r]:
             code[r] = NA
+    if detail is not None:
+        detail.update(bridges=dict(bridges), ladders=[list(L) for L in ladders], roots=[find(k) for k in range(len(ladders))])
     return np.array(code, np.uint8), partners, energies
 
 
