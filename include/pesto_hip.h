@@ -835,6 +835,65 @@ int pesto_lddt(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int
                int64_t K_in, const int64_t* offsets_in, const int32_t* j_in, const float* d_in, float* score_out,
                float* residue_out, int32_t* preserved_out, int32_t* total_out, int64_t* n_pairs_out, int32_t ptr_kind, void* stream);
 
+/* ---- essential dynamics of MD frames: fluctuations, covariance, cross-correlation, principal components (Amadei et al. 1993) ----
+ * Failures of the entry points below are reported through pesto_dynamics_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the cluster group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ *
+ * Definition (this library's own; the reference has none). xyz float32 [F,N,3]; sel int32 [n_sel] atom indices or NULL for all atoms
+ * (n_sel = N); x_f the selected coordinates of frame f flattened to m = 3 n_sel values. All arithmetic in double from the float32 inputs:
+ *     mean = (1/F) sum_f x_f        d_f = (double)x_f - mean (centred BEFORE multiplying)
+ *     C    = scale^2 sum_f d_f d_f^T / (F - ddof), ddof 0 or 1, F - ddof >= 1
+ * Every sum runs in an order fixed by the shapes alone (no floating-point atomics): every output is bit-identical from call to call. */
+const char* pesto_dynamics_last_error(void);
+
+enum {
+    PESTO_DYNAMICS_MAX_FRAMES = 1 << 24,      /* F */
+    PESTO_DYNAMICS_MAX_ATOMS = 1 << 24,       /* N */
+    PESTO_DYNAMICS_MAX_COV = 1 << 27,         /* (3 n_sel)^2 of pesto_covariance and pesto_cross_correlation: 1 GiB of doubles */
+    PESTO_DYNAMICS_MAX_COMPONENTS = 32        /* n_components of pesto_pca: half the solver's block of 64 vectors */
+};
+
+/* mean_out float32 [n_sel,3] = float32(mean), in the input's unit (unscaled); rmsf_out float32 [n_sel] =
+ * float32(scale sqrt((1/F) sum_f |d_f,i|^2)), each rounded once. */
+int pesto_fluctuations(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, double scale, float* mean_out,
+                       float* rmsf_out, int32_t ptr_kind, void* stream);
+
+/* C_out float64 [3 n_sel, 3 n_sel] = C. One 64 x 64 tile per workgroup on v_mfma_f64_16x16x4_f64, the frames staged through LDS and
+ * centred while staged; only the tiles i <= j are computed and mirrored, so C is bitwise symmetric. (3 n_sel)^2 <= PESTO_DYNAMICS_MAX_COV.
+ * Device scratch: 4 bytes per frame and selected coordinate. */
+int pesto_covariance(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, double scale, int32_t ddof, double* C_out,
+                     int32_t ptr_kind, void* stream);
+
+/* dccm_out float32 [n_sel,n_sel] = float32(tr C_ij / sqrt(tr C_ii tr C_jj)) over the 3 x 3 blocks of C (scale and ddof cancel), rounded
+ * once: bitwise symmetric, exactly 1 on the diagonal, 0 off the diagonal for an atom with zero variance (never NaN). C itself is device
+ * scratch, so (3 n_sel)^2 <= PESTO_DYNAMICS_MAX_COV. */
+int pesto_cross_correlation(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, float* dccm_out, int32_t ptr_kind,
+                            void* stream);
+
+/* The k = n_components leading eigenpairs of C, 1 <= k <= min(PESTO_DYNAMICS_MAX_COMPONENTS, 3 n_sel), by block subspace iteration with
+ * Rayleigh-Ritz on 64 vectors, matrix-free (C is never formed: Y = D^T (D Q) scale^2 / (F - ddof) per iteration; any F against 3 n_sel).
+ * The start block is a fixed counter hash; every block is orthonormalised twice through its 64 x 64 Gram matrix; the 64 x 64 eigenproblems
+ * are a one-sided Jacobi in one workgroup. At most max_iter >= 1 iterations; the done flag is read every fourth.
+ *     eig_out float64 [k]: the Ritz values theta, descending, >= 0
+ *     comp_out float64 [k,n_sel,3]: orthonormal rows; in each the entry of largest magnitude is positive (the lowest index on ties)
+ *     proj_out float32 [F,k] = float32(scale d_f . v_i)
+ *     mean_out float32 [n_sel,3] as pesto_fluctuations
+ *     resid_out float64 [k] = |C v_i - theta_i v_i|_2 as the iteration measures it (Y V - Q V Theta)
+ *     total_variance_out: one double in HOST memory, tr C
+ *     info_out int32 [4] in HOST memory: rank, iterations, converged, and the most sweeps any of the call's 64 x 64 Jacobi runs took
+ *         (a diagnostic: 60 is the cap)
+ * A direction i < k with theta_i <= 1e-12 theta_0 is a null direction: eigenvalue 0, residual 0, an all-zero component row; rank counts
+ * the others, rank <= min(k, F - 1, 3 n_sel). converged = (max_i resid_i <= tol theta_0), tol >= 0; it is reported, never an error. */
+int pesto_pca(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, int32_t n_components, double scale, int32_t ddof,
+              double tol, int32_t max_iter, double* eig_out, double* comp_out, float* proj_out, float* mean_out, double* resid_out,
+              double* total_variance_out, int32_t* info_out, int32_t ptr_kind, void* stream);
+
+/* proj_out float32 [F,k] = float32(scale ((double)x_f - (double)mean) . v_i) for a given basis: mean float32 [n_sel,3], components float64
+ * [k,n_sel,3], 1 <= k <= 64 (neither orthonormality nor a sign is required). The product of pesto_pca's projections. */
+int pesto_project(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, int32_t k, const float* mean,
+                  const double* components, double scale, float* proj_out, int32_t ptr_kind, void* stream);
+
 /* ---- hydrogen bonds and periodic unwrapping (hydrogen_bonds and unwrap_pbc of md_analysis/mdtraj_utils/trajectory_utils.py) ----
  * Failures of the entry points below are reported through pesto_hbonds_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after
