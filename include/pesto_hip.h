@@ -770,7 +770,8 @@ int pesto_dockq(pesto_model* m, int64_t F, int64_t N, const float* xyz_ref, cons
 /* replaces: the rmsd expression of trajectory_utils.py:328-338 behind a superposition on OTHER atoms than it measures, which neither the
  * reference's irmsd nor pesto_superpose offers (both fit and measure on one selection). xyz_ref [F_ref,N,3], F_ref = 1 or F; xyz [F,N,3];
  * sel_fit int32 [n_fit >= 3], sel_measure int32 [n_measure >= 1], in [0, N). rmsd_out float32 [F] = float32(sqrt(sum over sel_measure of
- * |x' - y|^2 / n_measure) scale), x' moved by the fit on sel_fit as in pesto_dockq, whose lrmsd_out this gives bit for bit for sel_R, sel_L. */
+ * |x' - y|^2 / n_measure) scale), x' moved by the fit on sel_fit - the one fit of pesto_superpose, pesto_rigid_docking, pesto_interface_rmsd and pesto_dockq (pesto_fit.h),
+ * so this is pesto_dockq's lrmsd_out bit for bit for sel_R, sel_L and pesto_interface_rmsd's rmsd_out for sel_measure = sel_fit. */
 int pesto_fit_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_fit, const int32_t* sel_fit,
                    int64_t n_measure, const int32_t* sel_measure, double scale, float* rmsd_out, int32_t ptr_kind, void* stream);
 

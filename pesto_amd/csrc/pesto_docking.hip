@@ -8,13 +8,15 @@
 // monotonic in s; the host derives s_star by bisection over the float bit patterns); only an emitted contact takes the root, in double and
 // rounded once to float32, which is the correctly rounded float32 root (53 >= 2 * 24 + 2 bits).
 // The lists come out of count -> scan -> emit with every position fixed by the scans; the residue pairs are the set bits of a per-frame
-// [Ra, Rb] bit map in index order, their minimum an integer atomicMin over the bits of the non-negative d; the pose is evaluated in double
-// in a fixed order. Every output is bit-identical from call to call.
+// [Ra, Rb] bit map in index order, their minimum an integer atomicMin over the bits of the non-negative d; the pose and the interface RMSD
+// are evaluated in double in a fixed order by the superposition fit of pesto_fit.h, the one pesto_trajectory.hip and pesto_dockq.hip
+// call (hence the interface RMSD's bits: pesto_superpose's off the reference frame, pesto_dockq's everywhere). Every output is
+// bit-identical from call to call.
 #include <cmath>
 
 #include "pesto_call.h"
 #include "pesto_cellgrid.h"      // (for the list protocol's scans only: there is no cell grid here)
-#include "pesto_geom.h"
+#include "pesto_fit.h"           // (and pesto_geom.h through it)
 
 namespace pesto {
 
@@ -201,10 +203,10 @@ __global__ __launch_bounds__(NT) void k_ia_flags(int N, int R, const int* __rest
 // ------------------------------------------------------------------------------------------------ rigid docking
 // replaces: interface_rigid_docking (trajectory_utils.py:474-499; two batched SVD superpositions with a transformed copy of the whole
 // trajectory between them, then scipy's rotation vector). One workgroup per frame, everything in double from the float32 inputs:
-//   1  fit the frame onto the reference on the receptor selection: t1, R1, t_ref1 - the sums, their order and the rotation are those
-//      of k_superpose_fit (pesto_trajectory.hip)
-//   2  x' = (x - t1) R1 + t_ref1 for the ligand selection only, recomputed in each pass instead of stored
-//   3  fit x' onto the reference's ligand selection: t_cm = mean(x'), t_ref2, R2
+//   1  fit the frame onto the reference on the receptor selection: t1, R1, t_ref1 - kabsch_fit of pesto_fit.h, the fit of
+//      k_superpose_fit (pesto_trajectory.hip) and of pesto_dockq.hip
+//   2  x' = (x - t1) R1 + t_ref1 for the ligand selection only (moved, pesto_fit.h), recomputed in each pass instead of stored
+//   3  fit x' onto the reference's ligand selection, the same function again: t_cm = mean(x'), t_ref2, R2
 //   4  t = t_ref2 - t_cm; r = the rotation vector of R2
 // A selection that equals the reference's bit for bit is fitted by the identity itself, not by a rotation within rounding of it (step 1:
 // x' = x; step 3: R2 = I), so a frame that is the reference gives t = 0 and r = 0 exactly.
@@ -233,103 +235,27 @@ __device__ void rotation_vector(const double* R, double* r) {
     for (int a = 0; a < 3; ++a) r[a] = v > 0.0 ? angle * (sign * q[a] / v) : 0.0;
 }
 
-// the selections' indices must lie in [0, N): checked before the fit dereferences them (error bit 0)
-__global__ __launch_bounds__(NT) void k_rd_check(int N, int nR, int nL, const int* __restrict__ sel_R, const int* __restrict__ sel_L,
-                                                 DkState* __restrict__ st) {
-    const int k = blockIdx.x * NT + threadIdx.x;
-    if (k >= nR + nL) return;
-    const int i = k < nR ? sel_R[k] : sel_L[k - nR];
-    if (i < 0 || i >= N) atomicOr(&st->err, 1);
-}
-
-// rmsd_out != NULL: the interface RMSD instead of the pose - step 1 on sel_R alone, then the deviation of the transformed selection from
-// the reference's as k_superpose_fit sums it (the same bits as pesto_superpose's rmsd_out), and exactly 0 for a selection that equals
-// the reference's bit for bit
+// the pose of every frame; behind k_index_check (pesto_fit.h), which refuses a selection index outside [0, N) before anything here
+// dereferences it. (The interface RMSD is k_fit_rmsd of pesto_fit.h, fitted and measured on the one selection.)
 __global__ __launch_bounds__(NT) void k_rigid_docking(int Fr, int N, int nR, int nL, const float* __restrict__ ref, const float* __restrict__ xyz,
-                                                      const int* __restrict__ sel_R, const int* __restrict__ sel_L, const DkState* __restrict__ st,
-                                                      float* __restrict__ t_out, float* __restrict__ r_out, float* __restrict__ rmsd_out,
-                                                      double scale) {
+                                                      const int* __restrict__ sel_R, const int* __restrict__ sel_L, const int* __restrict__ err,
+                                                      float* __restrict__ t_out, float* __restrict__ r_out) {
     __shared__ double red[NT / 64];
     __shared__ double sR[9];
-    if (st->err) return;
+    if (*err) return;
     const size_t f = blockIdx.x;
     const float* X = xyz + f * (size_t)N * 3;
     const float* Y = ref + (Fr == 1 ? 0 : f) * (size_t)N * 3;
-    // 1: the receptor fit
-    double m[6] = {0, 0, 0, 0, 0, 0}, differ = 0.0;
-    for (int k = threadIdx.x; k < nR; k += NT) {
-        const float* x = X + (size_t)sel_R[k] * 3;
-        const float* y = Y + (size_t)sel_R[k] * 3;
-        for (int c = 0; c < 3; ++c) { m[c] += (double)x[c]; m[3 + c] += (double)y[c]; differ += x[c] == y[c] ? 0.0 : 1.0; }
-    }
-    for (int c = 0; c < 6; ++c) m[c] = block_sum<NT>(m[c], red) / (double)nR;
-    const bool same1 = block_sum<NT>(differ, red) == 0.0;
-    if (!same1) {
-        double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = threadIdx.x; k < nR; k += NT) {
-            const float* x = X + (size_t)sel_R[k] * 3;
-            const float* y = Y + (size_t)sel_R[k] * 3;
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) H[3 * a + b] += ((double)y[a] - m[3 + a]) * ((double)x[b] - m[b]);
-        }
-        for (int c = 0; c < 9; ++c) H[c] = block_sum<NT>(H[c], red);
-        if (threadIdx.x == 0) kabsch_rotation(H, sR);
-    }
-    __syncthreads();
-    double R1[9];
-    for (int c = 0; c < 9; ++c) R1[c] = same1 ? (c % 4 == 0 ? 1.0 : 0.0) : sR[c];
-    __syncthreads();                    // (sR is written again below)
-    if (rmsd_out) {
-        double dev = 0.0;
-        if (!same1)
-            for (int k = threadIdx.x; k < nR; k += NT) {
-                const float* x = X + (size_t)sel_R[k] * 3;
-                const float* y = Y + (size_t)sel_R[k] * 3;
-                const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
-                for (int c = 0; c < 3; ++c) {
-                    const double e = ((d0 * R1[c] + d1 * R1[3 + c]) + d2 * R1[6 + c]) + m[3 + c] - (double)y[c];
-                    dev += e * e;
-                }
-            }
-        dev = block_sum<NT>(dev, red);
-        if (threadIdx.x == 0) rmsd_out[f] = (float)(sqrt(dev / (double)nR) * scale);
-        return;
-    }
-    // 2: a ligand atom in the receptor's frame
-    auto moved = [&](const float* x, double* p) {
-        if (same1) { p[0] = (double)x[0]; p[1] = (double)x[1]; p[2] = (double)x[2]; return; }
-        const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
-        for (int c = 0; c < 3; ++c) p[c] = ((d0 * R1[c] + d1 * R1[3 + c]) + d2 * R1[6 + c]) + m[3 + c];
-    };
-    // 3: the ligand fit
-    double g[6] = {0, 0, 0, 0, 0, 0};
-    differ = 0.0;
-    for (int k = threadIdx.x; k < nL; k += NT) {
-        const float* y = Y + (size_t)sel_L[k] * 3;
-        double p[3];
-        moved(X + (size_t)sel_L[k] * 3, p);
-        for (int c = 0; c < 3; ++c) { g[c] += p[c]; g[3 + c] += (double)y[c]; differ += p[c] == (double)y[c] ? 0.0 : 1.0; }
-    }
-    for (int c = 0; c < 6; ++c) g[c] = block_sum<NT>(g[c], red) / (double)nL;
-    const bool same2 = block_sum<NT>(differ, red) == 0.0;
-    if (!same2) {
-        double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = threadIdx.x; k < nL; k += NT) {
-            const float* y = Y + (size_t)sel_L[k] * 3;
-            double p[3];
-            moved(X + (size_t)sel_L[k] * 3, p);
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) H[3 * a + b] += ((double)y[a] - g[3 + a]) * (p[b] - g[b]);
-        }
-        for (int c = 0; c < 9; ++c) H[c] = block_sum<NT>(H[c], red);
-        if (threadIdx.x == 0) kabsch_rotation(H, sR);
-    }
-    // 4
-    if (threadIdx.x == 0) {
+    Fit rec, lig;
+    kabsch_fit<NT, true>(atoms(X, sel_R), atoms(Y, sel_R), nR, red, sR, rec);                                  // 1
+    const auto ligand = atoms(X, sel_L);
+    const auto moved_ligand = [=](int k, double* p) { double x[3]; ligand(k, x); moved(x, rec, p); };         // 2
+    kabsch_fit<NT, true>(moved_ligand, atoms(Y, sel_L), nL, red, sR, lig);                                     // 3
+    if (threadIdx.x == 0) {                                                                                    // 4
         double r[3] = {0.0, 0.0, 0.0};
-        if (!same2) rotation_vector(sR, r);
+        if (!lig.same) rotation_vector(sR, r);          // (lig.R where the fit left it: LDS takes rotation_vector's run-time indices)
         for (int c = 0; c < 3; ++c) {
-            t_out[f * 3 + c] = (float)(g[3 + c] - g[c]);
+            t_out[f * 3 + c] = (float)(lig.m[3 + c] - lig.m[c]);
             r_out[f * 3 + c] = (float)r[c];
         }
     }
@@ -487,7 +413,7 @@ int pesto_interface_atoms(pesto_model* m, int64_t N, const float* xyz0, int64_t 
 
 namespace {
 
-// the pose (t_out, r_out) or the interface RMSD (rmsd_out) of every frame: one launch of k_rigid_docking behind the index check
+// the pose (t_out, r_out: k_rigid_docking) or the interface RMSD (rmsd_out: k_fit_rmsd on sel_R alone) of every frame, behind the index check
 int launch_docking(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_R, const int32_t* sel_R,
                    int64_t n_L, const int32_t* sel_L, float* t_out, float* r_out, float* rmsd_out, double scale, int32_t ptr_kind, void* stream,
                    const char* what) {
@@ -495,21 +421,25 @@ int launch_docking(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const fl
     Buffers bf(ptr_kind, stream);
     const int iY = bf.input(xyz_ref, (size_t)F_ref * N * 12), iX = bf.input(xyz, (size_t)F * N * 12), iSr = bf.input(sel_R, (size_t)n_R * 4),
               iSl = bf.input(sel_L, (size_t)n_L * 4), iT = bf.output(t_out, (size_t)F * 12), iRv = bf.output(r_out, (size_t)F * 12),
-              iRm = bf.output(rmsd_out, (size_t)F * 4), iSt = bf.scratch(sizeof(DkState));
-    DkState hs = {};
+              iRm = bf.output(rmsd_out, (size_t)F * 4), iSt = bf.scratch(sizeof(int));
+    int herr = 0;
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<DkState>(iSt), 0, sizeof(DkState), bf.stm), what);
+    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSt), 0, sizeof(int), bf.stm), what);
     if (rc == 0) {
-        hipLaunchKernelGGL(k_rd_check, dim3(blocks((size_t)(n_R + n_L))), dim3(NT), 0, bf.stm, (int)N, (int)n_R, (int)n_L, bf.ptr<const int>(iSr),
-                           bf.ptr<const int>(iSl), bf.ptr<DkState>(iSt));
-        hipLaunchKernelGGL(k_rigid_docking, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_R, (int)n_L, bf.ptr<const float>(iY),
-                           bf.ptr<const float>(iX), bf.ptr<const int>(iSr), bf.ptr<const int>(iSl), bf.ptr<const DkState>(iSt), bf.ptr<float>(iT),
-                           bf.ptr<float>(iRv), bf.ptr<float>(iRm), scale);
+        const IndexLists idx = {{bf.ptr<const int>(iSr), bf.ptr<const int>(iSl)}, {n_R, n_L}};
+        hipLaunchKernelGGL(k_index_check<NT>, dim3(blocks((size_t)idx.total())), dim3(NT), 0, bf.stm, (int)N, idx, bf.ptr<int>(iSt));
+        if (t_out)
+            hipLaunchKernelGGL(k_rigid_docking, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_R, (int)n_L, bf.ptr<const float>(iY),
+                               bf.ptr<const float>(iX), bf.ptr<const int>(iSr), bf.ptr<const int>(iSl), bf.ptr<const int>(iSt), bf.ptr<float>(iT),
+                               bf.ptr<float>(iRv));
+        else
+            hipLaunchKernelGGL(k_fit_rmsd<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_R, (int)n_R, bf.ptr<const float>(iY),
+                               bf.ptr<const float>(iX), bf.ptr<const int>(iSr), bf.ptr<const int>(iSr), bf.ptr<const int>(iSt), scale, bf.ptr<float>(iRm));
         rc = hip_ok(hipGetLastError(), what);
     }
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(DkState));
+    if (rc == 0) rc = bf.read(iSt, &herr, sizeof(int));
     rc = bf.finish(rc, what);
-    if (rc == 0 && hs.err) rc = fail(PESTO_ERR_INVALID, "%s: atom indices of a selection must lie in [0, N)", what);
+    if (rc == 0 && herr) rc = fail(PESTO_ERR_INVALID, "%s: atom indices of a selection must lie in [0, N)", what);
     return rc;
 }
 

@@ -8,14 +8,13 @@
 // in a decoy when some atom pair of its two residues has s < s_star, s the float32 squared distance of pesto_geom.h and s_star the
 // smallest float at which fl32(sqrt_rn(s)) * scale < r_contact fails (contact_threshold), so the decision is the docking group's d < r_thr
 // exactly. The atoms come sorted by residue (a permutation; every pair holds two ranges of it), one wave owns a pair, its 64 lanes walk
-// the na * nb atom pairs 64 at a time and stop at the first step with a hit; the count is an integer sum. The two RMSDs restate the
-// selection fit of k_rigid_docking (pesto_docking.hip, step 1) as one device function - the same sums in the same order, the same
-// identity short cut - so the interface RMSD has the bits of pesto_interface_rmsd. No floating-point atomics: every output repeats its
-// bits from call to call.
+// the na * nb atom pairs 64 at a time and stop at the first step with a hit; the count is an integer sum. The two RMSDs are the fit, the
+// moved point and the deviation sum of pesto_fit.h, which pesto_docking.hip and pesto_trajectory.hip call too, so the interface RMSD
+// has the bits of pesto_interface_rmsd. No floating-point atomics: every output repeats its bits from call to call.
 #include <cmath>
 
 #include "pesto_call.h"
-#include "pesto_geom.h"
+#include "pesto_fit.h"
 
 namespace pesto {
 
@@ -25,19 +24,14 @@ constexpr int NT = 256;                 // threads per workgroup of every kernel
 constexpr int NW = NT / 64;             // its waves
 
 // ------------------------------------------------------------------------------------------------ the index check
-// Every index is validated before anything dereferences it, in the style of k_rd_check: the three selections and the permutation must
-// lie in [0, N) (error bit 0); a pair's two ranges must be non-empty ranges of the permutation with fewer than 2^31 atom pairs between
-// them (error bit 1). The kernels below return at once when a bit is set, so a refused call writes nothing.
-__global__ __launch_bounds__(NT) void k_dq_check(int N, long long nI, long long nR, long long nL, long long n_perm, long long P,
-                                                 const int* __restrict__ sel_I, const int* __restrict__ sel_R, const int* __restrict__ sel_L,
-                                                 const int* __restrict__ perm, const int* __restrict__ pairs, int* __restrict__ err) {
-    const long long k = (long long)blockIdx.x * NT + threadIdx.x;
-    const long long n_idx = nI + nR + nL + n_perm;
-    if (k < n_idx) {
-        const int i = k < nI ? sel_I[k] : k < nI + nR ? sel_R[k - nI] : k < nI + nR + nL ? sel_L[k - nI - nR] : perm[k - nI - nR - nL];
-        if (i < 0 || i >= N) atomicOr(err, 1);
-    } else if (k < n_idx + P) {
-        const int* q = pairs + 4 * (k - n_idx);
+// Every index is validated before anything dereferences it: the three selections and the permutation (idx) must lie in [0, N) (error
+// bit 0: check_index of pesto_fit.h); behind them, a pair's two ranges must be non-empty ranges of the permutation with fewer than 2^31
+// atom pairs between them (error bit 1). The kernels below return at once when a bit is set, so a refused call writes nothing.
+__global__ __launch_bounds__(NT) void k_dq_check(int N, IndexLists idx, long long n_perm, long long P, const int* __restrict__ pairs,
+                                                 int* __restrict__ err) {
+    long long k = (long long)blockIdx.x * NT + threadIdx.x;
+    if (!check_index(k, N, idx, err) && k < P) {
+        const int* q = pairs + 4 * k;
         const long long a0 = q[0], a1 = q[1], b0 = q[2], b1 = q[3];
         const bool ok = 0 <= a0 && a0 < a1 && a1 <= n_perm && 0 <= b0 && b0 < b1 && b1 <= n_perm && (a1 - a0) * (b1 - b0) <= 0x7fffffffLL;
         if (!ok) atomicOr(err, 2);
@@ -80,88 +74,6 @@ __device__ __forceinline__ int preserved_pairs(const float* __restrict__ X, cons
     return t;
 }
 
-// ------------------------------------------------------------------------------------------------ the selection fit
-// Step 1 of k_rigid_docking (pesto_docking.hip) as a device function: the frame X fitted onto the reference Y on the n atoms of sel, in
-// double from the float32 inputs - the means m (X's, then Y's), the covariance and its rotation R by the sums, their order and the
-// rotation of k_superpose_fit. A selection that equals the reference's bit for bit is fitted by the identity itself (same). red: NW
-// doubles of LDS, sR: 9; both are free for the next use on return.
-struct Fit {
-    double m[6], R[9];
-    bool same;
-};
-
-__device__ __forceinline__ void selection_fit(const float* __restrict__ X, const float* __restrict__ Y, const int* __restrict__ sel, int n, double* red,
-                                              double* sR, Fit& ft) {
-    double* m = ft.m;
-    double differ = 0.0;
-    for (int c = 0; c < 6; ++c) m[c] = 0.0;
-    for (int k = threadIdx.x; k < n; k += NT) {
-        const float* x = X + (size_t)sel[k] * 3;
-        const float* y = Y + (size_t)sel[k] * 3;
-        for (int c = 0; c < 3; ++c) { m[c] += (double)x[c]; m[3 + c] += (double)y[c]; differ += x[c] == y[c] ? 0.0 : 1.0; }
-    }
-    for (int c = 0; c < 6; ++c) m[c] = block_sum<NT>(m[c], red) / (double)n;
-    ft.same = block_sum<NT>(differ, red) == 0.0;
-    if (!ft.same) {
-        double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = threadIdx.x; k < n; k += NT) {
-            const float* x = X + (size_t)sel[k] * 3;
-            const float* y = Y + (size_t)sel[k] * 3;
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) H[3 * a + b] += ((double)y[a] - m[3 + a]) * ((double)x[b] - m[b]);
-        }
-        for (int c = 0; c < 9; ++c) H[c] = block_sum<NT>(H[c], red);
-        if (threadIdx.x == 0) kabsch_rotation(H, sR);
-    }
-    __syncthreads();
-    for (int c = 0; c < 9; ++c) ft.R[c] = ft.same ? (c % 4 == 0 ? 1.0 : 0.0) : sR[c];
-    __syncthreads();                    // (sR is free again)
-}
-
-// the summed squared deviation of the fitted selection itself from the reference's, as k_rigid_docking sums it for the interface RMSD
-// (the same bits); exactly 0 under the identity short cut
-__device__ __forceinline__ double fitted_deviation(const float* __restrict__ X, const float* __restrict__ Y, const int* __restrict__ sel, int n,
-                                                   const Fit& ft, double* red) {
-    const double* m = ft.m;
-    const double* R1 = ft.R;
-    double dev = 0.0;
-    if (!ft.same)
-        for (int k = threadIdx.x; k < n; k += NT) {
-            const float* x = X + (size_t)sel[k] * 3;
-            const float* y = Y + (size_t)sel[k] * 3;
-            const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
-            for (int c = 0; c < 3; ++c) {
-                const double e = ((d0 * R1[c] + d1 * R1[3 + c]) + d2 * R1[6 + c]) + m[3 + c] - (double)y[c];
-                dev += e * e;
-            }
-        }
-    return block_sum<NT>(dev, red);
-}
-
-// the summed squared deviation of ANOTHER selection, moved by the fit, from the reference's: x' is k_rigid_docking's `moved`, the atom
-// itself under the identity short cut, so a frame that is the reference gives exactly 0
-__device__ __forceinline__ double moved_deviation(const float* __restrict__ X, const float* __restrict__ Y, const int* __restrict__ sel, int n,
-                                                  const Fit& ft, double* red) {
-    const double* m = ft.m;
-    const double* R1 = ft.R;
-    auto moved = [&](const float* x, double* p) {
-        if (ft.same) { p[0] = (double)x[0]; p[1] = (double)x[1]; p[2] = (double)x[2]; return; }
-        const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
-        for (int c = 0; c < 3; ++c) p[c] = ((d0 * R1[c] + d1 * R1[3 + c]) + d2 * R1[6 + c]) + m[3 + c];
-    };
-    double dev = 0.0;
-    for (int k = threadIdx.x; k < n; k += NT) {
-        const float* y = Y + (size_t)sel[k] * 3;
-        double p[3];
-        moved(X + (size_t)sel[k] * 3, p);
-        for (int c = 0; c < 3; ++c) {
-            const double e = p[c] - (double)y[c];
-            dev += e * e;
-        }
-    }
-    return block_sum<NT>(dev, red);
-}
-
 // ------------------------------------------------------------------------------------------------ the score and the class
 // (fnat + 1 / (1 + (irmsd / 1.5)^2) + 1 / (1 + (lrmsd / 8.5)^2)) / 3 in double from the three float32 values, every operation rounded
 // as written (no contraction), rounded once to float32
@@ -197,10 +109,10 @@ __global__ __launch_bounds__(NT) void k_dockq(int N, int P, int nI, int nR, int 
     const float* X = xyz + f * (size_t)N * 3;
     const int kept = preserved_pairs(X, perm, pairs, P, s_star, ired);
     Fit ft;
-    selection_fit(X, ref, sel_I, nI, red, sR, ft);
-    const double dev_I = fitted_deviation(X, ref, sel_I, nI, ft, red);
-    selection_fit(X, ref, sel_R, nR, red, sR, ft);
-    const double dev_L = moved_deviation(X, ref, sel_L, nL, ft, red);
+    kabsch_fit<NT, true>(atoms(X, sel_I), atoms(ref, sel_I), nI, red, sR, ft);
+    const double dev_I = moved_deviation<NT>(atoms(X, sel_I), atoms(ref, sel_I), nI, ft, red);
+    kabsch_fit<NT, true>(atoms(X, sel_R), atoms(ref, sel_R), nR, red, sR, ft);
+    const double dev_L = moved_deviation<NT>(atoms(X, sel_L), atoms(ref, sel_L), nL, ft, red);
     if (threadIdx.x == 0) {
         const float fn = (float)((double)kept / (double)P);
         const float ir = (float)(sqrt(dev_I / (double)nI) * scale);
@@ -214,21 +126,8 @@ __global__ __launch_bounds__(NT) void k_dockq(int N, int P, int nI, int nR, int 
     }
 }
 
-// the RMSD of sel_M after the fit on sel_F: the ligand RMSD alone, and the general "different atoms for fit and measure"
-__global__ __launch_bounds__(NT) void k_fit_rmsd(int Fr, int N, int nF, int nM, const float* __restrict__ ref, const float* __restrict__ xyz,
-                                                 const int* __restrict__ sel_F, const int* __restrict__ sel_M, const int* __restrict__ err, double scale,
-                                                 float* __restrict__ rmsd_out) {
-    __shared__ double red[NW];
-    __shared__ double sR[9];
-    if (*err) return;
-    const size_t f = blockIdx.x;
-    const float* X = xyz + f * (size_t)N * 3;
-    const float* Y = ref + (Fr == 1 ? 0 : f) * (size_t)N * 3;
-    Fit ft;
-    selection_fit(X, Y, sel_F, nF, red, sR, ft);
-    const double dev = moved_deviation(X, Y, sel_M, nM, ft, red);
-    if (threadIdx.x == 0) rmsd_out[f] = (float)(sqrt(dev / (double)nM) * scale);
-}
+// (k_fit_rmsd, the RMSD of sel_M after the fit on sel_F - the ligand RMSD alone, and the general "different atoms for fit and measure":
+// pesto_fit.h)
 
 // ---- host side
 unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
@@ -274,9 +173,9 @@ int pesto_dockq(pesto_model* m, int64_t F, int64_t N, const float* xyz_ref, cons
     int rc = bf.upload();
     if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSt), 0, sizeof(int), bf.stm), "dockq");
     if (rc == 0) {
-        hipLaunchKernelGGL(k_dq_check, dim3(blocks((size_t)(n_I + n_R + n_L + n_perm + P))), dim3(NT), 0, bf.stm, (int)N, (long long)n_I, (long long)n_R,
-                           (long long)n_L, (long long)n_perm, (long long)P, bf.ptr<const int>(iSi), bf.ptr<const int>(iSr), bf.ptr<const int>(iSl),
-                           bf.ptr<const int>(iPm), bf.ptr<const int>(iPr), bf.ptr<int>(iSt));
+        const IndexLists idx = {{bf.ptr<const int>(iSi), bf.ptr<const int>(iSr), bf.ptr<const int>(iSl), bf.ptr<const int>(iPm)}, {n_I, n_R, n_L, n_perm}};
+        hipLaunchKernelGGL(k_dq_check, dim3(blocks((size_t)(idx.total() + P))), dim3(NT), 0, bf.stm, (int)N, idx, (long long)n_perm, (long long)P,
+                           bf.ptr<const int>(iPr), bf.ptr<int>(iSt));
         hipLaunchKernelGGL(k_dockq, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)N, (int)P, (int)n_I, (int)n_R, (int)n_L, bf.ptr<const float>(iY),
                            bf.ptr<const float>(iX), bf.ptr<const int>(iPm), bf.ptr<const int>(iPr), bf.ptr<const int>(iSi), bf.ptr<const int>(iSr),
                            bf.ptr<const int>(iSl), bf.ptr<const int>(iSt), s_star, scale, bf.ptr<float>(iFn), bf.ptr<int>(iKp), bf.ptr<float>(iIr),
@@ -304,10 +203,9 @@ int pesto_fit_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const fl
     int rc = bf.upload();
     if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSt), 0, sizeof(int), bf.stm), "fit_rmsd");
     if (rc == 0) {
-        hipLaunchKernelGGL(k_dq_check, dim3(blocks((size_t)(n_fit + n_measure))), dim3(NT), 0, bf.stm, (int)N, 0LL, (long long)n_fit, (long long)n_measure,
-                           0LL, 0LL, (const int*)nullptr, bf.ptr<const int>(iSf), bf.ptr<const int>(iSm), (const int*)nullptr, (const int*)nullptr,
-                           bf.ptr<int>(iSt));
-        hipLaunchKernelGGL(k_fit_rmsd, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_fit, (int)n_measure, bf.ptr<const float>(iY),
+        const IndexLists idx = {{bf.ptr<const int>(iSf), bf.ptr<const int>(iSm)}, {n_fit, n_measure}};
+        hipLaunchKernelGGL(k_index_check<NT>, dim3(blocks((size_t)idx.total())), dim3(NT), 0, bf.stm, (int)N, idx, bf.ptr<int>(iSt));
+        hipLaunchKernelGGL(k_fit_rmsd<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_fit, (int)n_measure, bf.ptr<const float>(iY),
                            bf.ptr<const float>(iX), bf.ptr<const int>(iSf), bf.ptr<const int>(iSm), bf.ptr<const int>(iSt), scale, bf.ptr<float>(iO));
         rc = hip_ok(hipGetLastError(), "fit_rmsd: launch failed");
     }

@@ -1,6 +1,8 @@
-// pesto_geom.h - the geometry the MD analysis groups share (pesto_trajectory.hip, pesto_docking.hip, pesto_hbonds.hip): the float32 squared distance of
-// NumPy and torch, the host's derivation of squared-distance thresholds from it, the workgroup sum in double and the rotation of a
-// Kabsch superposition. Also one edge of the model's geometry (r, |r|, the fix-up) for the backward of the geometry pass (pesto_train.hip).
+// pesto_geom.h - the geometry the analysis groups share (pesto_hbonds.hip, pesto_lddt.hip, pesto_cluster.hip, pesto_peaks.hip,
+// pesto_dynamics.hip, and pesto_trajectory.hip, pesto_docking.hip and pesto_dockq.hip through pesto_fit.h): the float32 squared distance
+// of NumPy and torch, the host's derivation of squared-distance thresholds from it, the workgroup sum in double and the rotation of a
+// Kabsch superposition (kabsch_rotation: called by the one superposition fit, pesto_fit.h; kabsch_trace: pesto_cluster.hip). Also one
+// edge of the model's geometry (r, |r|, the fix-up) for the backward of the geometry pass (pesto_train.hip).
 //
 // Everything sits in an anonymous namespace (one copy per translation unit, like pesto_call.h).
 #pragma once

@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "pesto_call.h"
-#include "pesto_geom.h"
+#include "pesto_fit.h"           // (and pesto_geom.h through it)
 
 namespace pesto {
 
@@ -262,12 +262,13 @@ __global__ __launch_bounds__(NT) void k_sum_i64(int n, const long long* __restri
     if (threadIdx.x == 0) out[0] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// ---- superposition (the rotation of a covariance: kabsch_rotation of pesto_geom.h)
+// ---- superposition (kabsch_fit, moved and moved_deviation of pesto_fit.h, shared with pesto_docking.hip and pesto_dockq.hip)
 // replaces: superpose_transform and the rmsd expression (trajectory_utils.py:190-207, 308-325). One workgroup per frame over the n_sel
-// selected atoms: means, covariance, rotation, then the deviation of the transformed selection from the reference's. tr [F][15] keeps
-// t, R, t_ref in double for k_superpose_apply.
+// selected atoms, which may differ on the two sides: the fit without the identity short cut (a frame that is the reference gets its
+// rotation within rounding of I, as it always has), then the deviation of the transformed selection from the reference's. tr [F] keeps
+// the fit (t, R, t_ref in double) for k_superpose_apply.
 __global__ __launch_bounds__(NT) void k_superpose_fit(int Fr, int Nr, int N, int n_sel, const float* __restrict__ ref, const float* __restrict__ xyz,
-                                                      const int* __restrict__ sel_ref, const int* __restrict__ sel, double* __restrict__ tr,
+                                                      const int* __restrict__ sel_ref, const int* __restrict__ sel, Fit* __restrict__ tr,
                                                       float* __restrict__ t_out, float* __restrict__ R_out, float* __restrict__ tref_out,
                                                       float* __restrict__ rmsd, double scale) {
     __shared__ double red[NT / 64];
@@ -275,53 +276,29 @@ __global__ __launch_bounds__(NT) void k_superpose_fit(int Fr, int Nr, int N, int
     const size_t f = blockIdx.x;
     const float* X = xyz + f * (size_t)N * 3;
     const float* Y = ref + (Fr == 1 ? 0 : f) * (size_t)Nr * 3;
-    double m[6] = {0, 0, 0, 0, 0, 0};
-    for (int k = threadIdx.x; k < n_sel; k += NT) {
-        const float* x = X + (size_t)(sel ? sel[k] : k) * 3;
-        const float* y = Y + (size_t)(sel_ref ? sel_ref[k] : k) * 3;
-        for (int c = 0; c < 3; ++c) { m[c] += (double)x[c]; m[3 + c] += (double)y[c]; }
-    }
-    for (int c = 0; c < 6; ++c) m[c] = block_sum<NT>(m[c], red) / (double)n_sel;
-    double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = threadIdx.x; k < n_sel; k += NT) {
-        const float* x = X + (size_t)(sel ? sel[k] : k) * 3;
-        const float* y = Y + (size_t)(sel_ref ? sel_ref[k] : k) * 3;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) H[3 * a + b] += ((double)y[a] - m[3 + a]) * ((double)x[b] - m[b]);
-    }
-    for (int c = 0; c < 9; ++c) H[c] = block_sum<NT>(H[c], red);
+    const auto px = atoms<true>(X, sel), py = atoms<true>(Y, sel_ref);
+    Fit ft;
+    kabsch_fit<NT, false>(px, py, n_sel, red, sR, ft);
     if (threadIdx.x == 0) {
-        double R[9];
-        kabsch_rotation(H, R);
-        for (int c = 0; c < 9; ++c) { sR[c] = R[c]; tr[f * 15 + 3 + c] = R[c]; R_out[f * 9 + c] = (float)R[c]; }
+        for (int c = 0; c < 9; ++c) R_out[f * 9 + c] = (float)ft.R[c];
         for (int c = 0; c < 3; ++c) {
-            tr[f * 15 + c] = m[c]; tr[f * 15 + 12 + c] = m[3 + c];
-            t_out[f * 3 + c] = (float)m[c];
-            if (Fr != 1 || f == 0) tref_out[f * 3 + c] = (float)m[3 + c];
+            t_out[f * 3 + c] = (float)ft.m[c];
+            if (Fr != 1 || f == 0) tref_out[f * 3 + c] = (float)ft.m[3 + c];
         }
+        tr[f] = ft;
     }
-    __syncthreads();
-    double dev = 0.0;
-    for (int k = threadIdx.x; k < n_sel; k += NT) {
-        const float* x = X + (size_t)(sel ? sel[k] : k) * 3;
-        const float* y = Y + (size_t)(sel_ref ? sel_ref[k] : k) * 3;
-        const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
-        for (int c = 0; c < 3; ++c) {
-            const double e = ((d0 * sR[c] + d1 * sR[3 + c]) + d2 * sR[6 + c]) + m[3 + c] - (double)y[c];
-            dev += e * e;
-        }
-    }
-    dev = block_sum<NT>(dev, red);
+    const double dev = moved_deviation<NT>(px, py, n_sel, ft, red);
     if (threadIdx.x == 0) rmsd[f] = (float)(sqrt(dev / (double)n_sel) * scale);
 }
 
 // out[f, n, :] = (xyz[f, n, :] - t[f]) R[f] + t_ref[f], in double from the fit's double t, R, t_ref
-__global__ __launch_bounds__(NT) void k_superpose_apply(size_t total, int N, const float* __restrict__ xyz, const double* __restrict__ tr, float* __restrict__ out) {
+__global__ __launch_bounds__(NT) void k_superpose_apply(size_t total, int N, const float* __restrict__ xyz, const Fit* __restrict__ tr, float* __restrict__ out) {
     const size_t k = (size_t)blockIdx.x * NT + threadIdx.x;
     if (k >= total) return;
-    const double* T = tr + (k / (size_t)N) * 15;
-    const double d0 = (double)xyz[3 * k] - T[0], d1 = (double)xyz[3 * k + 1] - T[1], d2 = (double)xyz[3 * k + 2] - T[2];
-    for (int c = 0; c < 3; ++c) out[3 * k + c] = (float)(((d0 * T[3 + c] + d1 * T[6 + c]) + d2 * T[9 + c]) + T[12 + c]);
+    const double x[3] = {(double)xyz[3 * k], (double)xyz[3 * k + 1], (double)xyz[3 * k + 2]};
+    double p[3];
+    moved(x, tr[k / (size_t)N], p);
+    for (int c = 0; c < 3; ++c) out[3 * k + c] = (float)p[c];
 }
 
 // replaces: Xp = X M / count of md_analysis/apply_model_md.ipynb. One thread per (frame, residue): its atoms (perm, in atom order) summed in double
@@ -526,16 +503,16 @@ int pesto_superpose(pesto_model* m, int64_t F, int64_t F_ref, int64_t N_ref, int
     const int iY = bf.input(xyz_ref, (size_t)F_ref * N_ref * 12), iX = bf.input(xyz, (size_t)F * N * 12);
     const int iSr = bf.input(sel_ref, (size_t)n_sel * 4), iS = bf.input(sel, (size_t)n_sel * 4);
     const int it = bf.output(t_out, (size_t)F * 12), iR = bf.output(R_out, (size_t)F * 36), itr = bf.output(t_ref_out, (size_t)F_ref * 12),
-              iO = bf.output(xyz_out, (size_t)F * N * 12), iD = bf.output(rmsd_out, (size_t)F * 4), iW = bf.scratch((size_t)F * 15 * 8);
+              iO = bf.output(xyz_out, (size_t)F * N * 12), iD = bf.output(rmsd_out, (size_t)F * 4), iW = bf.scratch((size_t)F * sizeof(Fit));
     int rc = bf.upload();
     if (rc == 0) {
         hipLaunchKernelGGL(k_superpose_fit, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N_ref, (int)N, (int)n_sel, bf.ptr<const float>(iY),
-                           bf.ptr<const float>(iX), sel_ref ? bf.ptr<const int>(iSr) : nullptr, sel ? bf.ptr<const int>(iS) : nullptr, bf.ptr<double>(iW),
+                           bf.ptr<const float>(iX), sel_ref ? bf.ptr<const int>(iSr) : nullptr, sel ? bf.ptr<const int>(iS) : nullptr, bf.ptr<Fit>(iW),
                            bf.ptr<float>(it), bf.ptr<float>(iR), bf.ptr<float>(itr), bf.ptr<float>(iD), scale);
         if (xyz_out) {
             const size_t total = (size_t)F * N;
             hipLaunchKernelGGL(k_superpose_apply, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, bf.stm, total, (int)N, bf.ptr<const float>(iX),
-                               bf.ptr<const double>(iW), bf.ptr<float>(iO));
+                               bf.ptr<const Fit>(iW), bf.ptr<float>(iO));
         }
     }
     return bf.finish(rc, "superpose");

@@ -71,7 +71,7 @@ def timed(fn, reps, warm=2):
 
 def source_hash():
     h = hashlib.sha256()
-    for rel in ("pesto_amd/csrc/pesto_docking.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/docking.py", "profiles/bench_docking.py"):
+    for rel in ("pesto_amd/csrc/pesto_docking.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/csrc/pesto_fit.h", "pesto_amd/docking.py", "profiles/bench_docking.py"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 

@@ -99,7 +99,7 @@ def complex_of(F, N, seed):
 
 def source_hash():
     h = hashlib.sha256()
-    for rel in ("pesto_amd/csrc/pesto_dockq.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/csrc/pesto_call.h", "pesto_amd/dockq.py", "profiles/bench_dockq.py"):
+    for rel in ("pesto_amd/csrc/pesto_dockq.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/csrc/pesto_fit.h", "pesto_amd/csrc/pesto_call.h", "pesto_amd/dockq.py", "profiles/bench_dockq.py"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 

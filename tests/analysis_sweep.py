@@ -26,6 +26,7 @@ Edge sets (the constants are read from the sources named; tests assert the cover
                           acceptor blocks), LIST_SCAN_NT = 1024 (pesto_cellgrid.h: frames of frame_hbonds, donor pairs of the occupancy list)
     pesto_docking.hip     FC_ROWS = 8, FC_TILE = 32, 64-lane partner walk, NT = 256 (k_frame_scan over Na), SCAN_NT = 1024 (over F)
     pesto_sasa.hip        NT = 256, WAVES = 4 atoms per workgroup, TILE = 256 candidate records, MB = 64 points per mask
+    pesto_fit.h           NT = 256 threads stride a selection (the superposition fit of the trajectory, docking and DockQ groups), 64-lane waves
     pesto_cellgrid.h      GRID_MAX = 64 cells per axis, 2 N + 64 cells, h *= 1.25f, 256-thread setup / count, 1024-thread k_grid_scan
 """
 import functools
@@ -664,7 +665,7 @@ def build_cellgrid(case):
     return drawn(draw, seed)
 
 
-# ================================================================== kabsch_rotation through its three users
+# ================================================================== kabsch_rotation through the one fit (pesto_fit.h) and its three users
 # shape (selected atoms, F, 'one' reference frame | a reference 'per' frame)
 SUPERPOSE = (
     ("generic", 201, (3, 1, "one")),
@@ -691,6 +692,9 @@ SUPERPOSE = (
     ("far9k", 222, (3, 1, "one")),
     ("small", 223, (64, 5, "per")),
     ("small", 224, (300, 1, "one")),
+    ("generic", 225, (255, 2, "one")),          # the workgroup edge (NT = 256 threads stride the selection): one short of it,
+    ("generic", 226, (256, 2, "per")),          # ... on it,
+    ("generic", 227, (257, 2, "one")),          # ... and one thread with a second atom
 )
 SYMMETRIC = dict(square=[(1, 1, 0), (-1, 1, 0), (-1, -1, 0), (1, -1, 0)], tetrahedron=[(1, 1, 1), (1, -1, -1), (-1, 1, -1), (-1, -1, 1)],
                  cube=[(a, b, c) for a in (-1, 1) for b in (-1, 1) for c in (-1, 1)])
@@ -877,7 +881,7 @@ REQUIRED = {
     ("sasa", "sizes"): {1, 2, 63, 64, 65, 257, 300}, ("sasa", "structures"): {1, 2, 3, 5}, ("sasa", "F"): {1, 3}, ("sasa", "points"): {1, 64, 96, 100},
     ("cellgrid", "assemblies"): {1, 3, 4, 5, 6, 2}, ("cellgrid", "kind"): {"cube", "rod", "slab", "point", "corner", "budget", "big"},
     ("cellgrid", "atoms"): {2, 3, 255, 256, 257, 600},
-    ("superpose", "atoms"): {3, 4, 64, 65, 300}, ("superpose", "F"): {1, 5}, ("superpose", "reference"): {"one", "per"},
+    ("superpose", "atoms"): {3, 4, 64, 65, 255, 256, 257, 300}, ("superpose", "F"): {1, 2, 5}, ("superpose", "reference"): {"one", "per"},
     ("superpose", "family"): {"generic", "rot180", "identity", "mirror", "mirror+noise", "planar", "planar+mirror", "slab2", "slab4+mirror", "slab7",
                               "collinear", "square", "tetrahedron", "cube", "far9k", "small"},
 }

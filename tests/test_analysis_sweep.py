@@ -374,6 +374,12 @@ def test_superposition_families(case):
         rm_bound = 4 * EPS32 * max(float(np.abs(c["rmsd64"]).max()), biggest)
         close(case, "rmsd", rm, c["rmsd64"], rm_bound)
         close(case, "irmsd", irm, c["irmsd64"], rm_bound)
+        # one fit behind both: the same bits wherever the selection is not its reference's value for value (frames 1: of every family
+        # but identity, whose frames all are), and there irmsd's identity short cut gives exactly 0
+        moved = (c["xyz"][:, sel] != c["ref"][:, sel]).any((1, 2))
+        assert moved[1:].all() or case[0] == "identity", case
+        exact(case, "rmsd against irmsd off the reference", rm[moved], irm[moved])
+        exact(case, "irmsd of a frame that is its reference", irm[~moved], np.zeros(int((~moved).sum()), np.float32))
         close(case, "t", t, c["t64"], bound4(c["t64"]))
         close(case, "t_ref", tr, c["tr64"], bound4(c["tr64"]))
         # where the covariance fixes the rotation: R, the superposed coordinates of all atoms, the rigid docking

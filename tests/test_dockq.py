@@ -3,7 +3,7 @@ tensors: a seeded sweep over the number of decoys, of native pairs and of backbo
 workgroup (256) - native pairs, preserved and fnat exactly, irmsd bit for bit against docking.irmsd on the GPU, lrmsd within the bound
 tests/test_docking.py allows irmsd against its float64 restatement (max(4 e_ref, 4 eps32 max|value|), the worst share printed), the score
 within one float32 unit and the class exactly from the returned values; the hand-worked cases; rigid motions; the recorded systems
-against native_contacts over residue_contact_maps; fit_rmsd against trajectory.rmsd; identical bits from call to call and between the
+against native_contacts over residue_contact_maps; fit_rmsd bit for bit against docking.irmsd and trajectory.rmsd; identical bits from call to call and between the
 two sides; and a refused call, which writes nothing."""
 import numpy as np
 import pytest
@@ -162,6 +162,7 @@ def test_recorded_systems_against_native_contacts_over_the_full_maps(name, on_de
 
 @pytest.mark.parametrize("on_device", [False, True], ids=["host", "device"])
 def test_fit_rmsd(on_device):
+    from pesto_amd import docking as D
     from pesto_amd import dockq as Q
     from pesto_amd import trajectory as T
     s = sweep_system(65, 2, 257, 255)
@@ -169,11 +170,17 @@ def test_fit_rmsd(on_device):
     for z in (s, big):
         xyz = dev(z["xyz"]) if on_device else z["xyz"]
         S_R, S_L = backbone_def(z["ids_R"], z["ids_L"], z["bb"])
-        # fit and measure on the same atoms: trajectory.rmsd, within the bound (exactly 0 against some 1e-15 for the reference itself)
+        # fit and measure on the same atoms: docking's interface RMSD on that selection (a threshold beyond every distance makes every
+        # atom an interface atom, the mask picks S_R) bit for bit, and trajectory.rmsd bit for bit off the reference frame, where the
+        # identity short cut gives exactly 0 against trajectory.rmsd's some 1e-15
         both = Q.fit_rmsd(xyz[:1], xyz, S_R, S_R)
         plain = T.rmsd(xyz[:1], xyz, S_R, S_R)
+        only_R = np.zeros(z["xyz"].shape[1], bool)
+        only_R[S_R] = True
         assert (both.is_cuda if on_device else isinstance(both, np.ndarray)) and host(both).dtype == np.float32
-        assert np.abs(host(both).astype(np.float64) - host(plain)).max() <= bound(host(plain)) and host(both)[0] == 0
+        assert same_bits(both, D.irmsd(xyz[:1], xyz, z["ids_R"], z["ids_L"], z["roa"], only_R, r_thr=1e6))
+        assert same_bits(host(both)[1:], host(plain)[1:]) and host(both)[0] == 0
+        assert np.abs(host(both).astype(np.float64) - host(plain)).max() <= bound(host(plain))
         want = fit_rmsd_def(z["xyz"][:1], z["xyz"], S_R, S_R)
         assert np.abs(host(both).astype(np.float64) - want).max() <= bound(want)
         # the ligand RMSD is fit_rmsd on S_R and S_L, bit for bit, here and in dockq
