@@ -41,28 +41,11 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .trajectory import _model_of, _xyz
+from .trajectory import _model_of, _selection, _xyz
 
 MAX_PAIRS = 2 ** 28         # PESTO_CLUSTER_MAX_PAIRS: Fa * Fb of pairwise_rmsd
 MAX_FRAMES = 16384          # PESTO_CLUSTER_MAX_FRAMES: F of gromos_clusters
 F32_MAX = float(np.finfo(np.float32).max)
-
-
-def _sel(sel, n_atoms):
-    if sel is None:
-        return None, n_atoms
-    s = _lib.host(sel).reshape(-1)
-    if s.dtype == np.bool_:
-        if s.size != n_atoms:
-            raise ValueError(f"sel: a mask must have {n_atoms} entries, got {s.size}")
-        s = np.nonzero(s)[0]
-    if not np.issubdtype(s.dtype, np.integer):
-        raise ValueError(f"sel must hold atom indices or be a mask, got {s.dtype}")
-    if not 1 <= s.size <= n_atoms:
-        raise ValueError(f"sel must select 1 to {n_atoms} atoms, got {s.size}")
-    if s.min() < 0 or s.max() >= n_atoms:
-        raise ValueError(f"sel: atom indices must lie in 0 .. {n_atoms - 1}")
-    return np.ascontiguousarray(s, np.int32), int(s.size)
 
 
 def _check_rmsd(xyz_a, xyz_b, sel, scale):
@@ -74,7 +57,7 @@ def _check_rmsd(xyz_a, xyz_b, sel, scale):
         raise ValueError(f"xyz_a has {N} atoms and xyz_b {int(b.shape[1])}")
     if Fa * Fb > MAX_PAIRS:
         raise ValueError(f"at most 2**28 frame pairs, got {Fa} * {Fb}")
-    s, n = _sel(sel, N)
+    s, n = _selection(sel, N, "sel", least=1)
     sc = float(scale)
     if not (np.isfinite(sc) and abs(sc) <= F32_MAX):
         raise ValueError(f"scale must be finite, got {scale!r}")

@@ -6,7 +6,7 @@
 // pairwise_rmsd   k_prmsd_pack   per frame: the selected atoms as rows (x, y, z, 1) of a [16 frames][atom][64] float32 image, the atoms
 //                                padded with zero columns to a multiple of 4, the frames with zero frames to a multiple of 16; and
 //                                G_f = sum |x - mean|^2 in double
-//                 k_prmsd_cov    one workgroup per 16 x 16 frame pairs: the [64 x n] . [n x 64] product on v_mfma_f64_16x16x4_f64 from the
+//                 k_prmsd_cov    one workgroup per 16 x 16 frame pairs: the [64 x n] . [n x 64] product as one tile of pesto_mma64.h from the
 //                                float32 rows converted to double (every product exact, only the accumulation rounds). Each pair's 4 x 4
 //                                block holds H uncentred, both coordinate sums and n; the epilogue hands one pair to every thread:
 //                                H - s_a s_b^T / n, its singular values by one-sided Jacobi (kabsch_trace, pesto_geom.h) and
@@ -20,6 +20,7 @@
 
 #include "pesto_call.h"
 #include "pesto_geom.h"
+#include "pesto_mma64.h"
 
 namespace pesto {
 namespace {
@@ -27,12 +28,8 @@ namespace {
 constexpr int NT = 256;
 constexpr int TF = 16;          // frames on a tile side
 constexpr int TR = 4 * TF;      // rows on a tile side: (x, y, z, 1) per frame
-constexpr int KC = 16;          // atoms per LDS stage
-constexpr int LS = 80;          // doubles between two atoms of a staged tile: the 4 atoms of one MFMA step fall on both halves of the banks
-constexpr int HS = TR + 1;      // doubles between two rows of the accumulator image
 constexpr int ROUNDS = 32;      // clustering rounds enqueued between two reads of the done flag
-
-using f64x4 = __attribute__((ext_vector_type(4))) double;
+static_assert(TR == MT, "16 frames are one tile of pesto_mma64.h");
 
 // ---- pairwise RMSD
 // One workgroup per frame slot f of [0, 16 T): the image Pk[f / 16][k][4 (f % 16) + c] and G[f]. A slot beyond F is all zeros.
@@ -68,57 +65,29 @@ __global__ __launch_bounds__(NT) void k_prmsd_pack(int F, int N, int n, int npad
     if (threadIdx.x == 0) G[f] = g;
 }
 
-// stage KC atoms x 64 rows of a tile: one float4 (one frame's row group of one atom) per thread, as doubles
+// a stage's operand, KC atoms x 64 rows of a tile: one float4 (one frame's row group of one atom) per thread, converted to double when staged
 __device__ __forceinline__ float4 stage_load(const float* __restrict__ tile, int k0, int npad) {
     const int kk = threadIdx.x >> 4;
     if (k0 + kk >= npad) return make_float4(0.f, 0.f, 0.f, 0.f);
     return ((const float4*)(tile + (size_t)(k0 + kk) * TR))[threadIdx.x & 15];
 }
-__device__ __forceinline__ void stage_store(double* S, float4 v) {
-    double* d = S + (threadIdx.x >> 4) * LS + 4 * (threadIdx.x & 15);
-    d[0] = (double)v.x; d[1] = (double)v.y; d[2] = (double)v.z; d[3] = (double)v.w;
-}
 
-// Workgroup (ti, tj): the 16 frames 16 ti .. of A against the 16 frames 16 tj .. of B. Wave w owns the rows of A's frames 4 w .. 4 w + 3
-// against all 64 rows of B (four 16 x 16 accumulators). self: only tj >= ti and within a diagonal tile only j >= i are evaluated and
-// written to both D[i,j] and D[j,i]; the diagonal is 0.
+// Workgroup (ti, tj): the 16 frames 16 ti .. of A against the 16 frames 16 tj .. of B, one tile of pesto_mma64.h (wave w: the rows of A's
+// frames 4 w .. 4 w + 3 against all 64 rows of B). self: only tj >= ti and within a diagonal tile only j >= i are evaluated and written
+// to both D[i,j] and D[j,i]; the diagonal is 0.
 __global__ __launch_bounds__(NT) void k_prmsd_cov(int Fa, int Fb, int Tb, int n, int npad, const float* __restrict__ Pa, const float* __restrict__ Pb,
                                                   const double* __restrict__ Ga, const double* __restrict__ Gb, double scale, int self,
                                                   float* __restrict__ D) {
-    __shared__ double lds[TR * HS];             // the staged tiles (2 x KC x LS doubles), then the accumulator image (TR x HS)
-    static_assert(2 * KC * LS <= TR * HS, "the staged tiles must fit the accumulator image");
+    __shared__ double lds[MMA64_LDS];           // the staged tiles, then the accumulator image (TR x HS)
     const int ti = blockIdx.x / Tb, tj = blockIdx.x % Tb;
     if (self && tj < ti) return;
-    double* As = lds;
-    double* Bs = lds + KC * LS;
-    const float* ta = Pa + (size_t)ti * npad * TR;
-    const float* tb = Pb + (size_t)tj * npad * TR;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+    const float *ta = Pa + (size_t)ti * npad * TR, *tb = Pb + (size_t)tj * npad * TR;
+    auto load = [&](int k0, float4& ra, float4& rb) { ra = stage_load(ta, k0, npad); rb = stage_load(tb, k0, npad); };
+    auto store = [](double* As, const float4& ra) { store_kmajor(As, ra); };
     f64x4 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = f64x4{0.0, 0.0, 0.0, 0.0};
-    float4 ra = stage_load(ta, 0, npad), rb = stage_load(tb, 0, npad);
-    for (int k0 = 0; k0 < npad; k0 += KC) {
-        __syncthreads();
-        stage_store(As, ra);
-        stage_store(Bs, rb);
-        __syncthreads();
-        if (k0 + KC < npad) { ra = stage_load(ta, k0 + KC, npad); rb = stage_load(tb, k0 + KC, npad); }
-        const int steps = min(KC, npad - k0) >> 2;          // npad is a multiple of 4: the atoms' tail is zero columns of the image
-        for (int s = 0; s < steps; ++s) {
-            const double* a_row = As + (4 * s + lk) * LS;
-            const double* b_row = Bs + (4 * s + lk) * LS;
-            const double a = a_row[16 * w + lr];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b_row[16 * c + lr], acc[c], 0, 0, 0);
-        }
-    }
+    mma64_loop<float4, true>(lds, 0, npad, load, store, acc);            // npad is a multiple of 4: the atoms' tail is zero columns of the image
     __syncthreads();
-    // C/D of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 reg
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lds[(16 * w + lk + 4 * r) * HS + 16 * c + lr] = acc[c][r];
+    mma64_store(acc, lds, HS, 1.0);
     __syncthreads();
     const int fa = threadIdx.x >> 4, fb = threadIdx.x & 15;
     const int i = ti * TF + fa, j = tj * TF + fb;

@@ -7,14 +7,14 @@
 //
 // k_dyn_mean      per coordinate: the mean and sum_f d^2 over the frames in a fixed order, and the selected coordinates packed as a
 //                 [F][mp] float32 image (mp = m padded to a multiple of 64 with zero columns whose mean is 0)
-// k_dyn_mma<MODE> ONE tile skeleton for the four tall products: a 64 x 64 tile on v_mfma_f64_16x16x4_f64, K staged through LDS 16 deep,
-//                 the operands centred while they are staged (the K tail is zero rows of d, not of x):
+// k_dyn_mma<MODE> ONE tile skeleton for the four tall products: the 64 x 64 double-precision tile of pesto_mma64.h (K staged through LDS
+//                 16 deep), the operands centred while they are loaded (the K tail is zero rows of d, not of x):
 //                     GRAM  [m x F] . [F x m]   covariance: only the tiles i <= j, mirrored through LDS, so C is bitwise symmetric
 //                     DQ    [F x m] . [m x 64]  D Q of the solver, and every projection
 //                     DTZ   [m x F] . [F x 64]  D^T (D Q)
 //                     QTY   [64 x m] . [m x 64] Q^T Y and the Gram matrix Y^T Y of the orthonormalisation
 //                 the last three split K over blockIdx.y into partial tiles that k_dyn_reduce adds in a fixed order (no float atomics)
-// k_dyn_jacobi    one workgroup: the eigenvectors of a symmetric 64 x 64 matrix by one-sided Jacobi (the idiom of pesto_geom.h: columns of
+// k_dyn_jacobi    one workgroup: the eigenvectors of a symmetric 64 x 64 matrix by one-sided Jacobi (jacobi_angle of pesto_geom.h: columns of
 //                 A V rotated until orthogonal to JTOL), 32 disjoint column pairs per step in round-robin order, sorted descending
 // k_dyn_rotate    Out = In . V (. diag(1 / sqrt(s)) with the directions below a relative threshold zeroed: the orthonormalisation, whose
 //                 Gram matrix is scaled to a unit diagonal before its Jacobi; twice, then one Newton-Schulz step, k_dyn_polish)
@@ -28,15 +28,13 @@
 
 #include "pesto_call.h"
 #include "pesto_geom.h"
+#include "pesto_mma64.h"
 
 namespace pesto {
 namespace {
 
 constexpr int NT = 256;
-constexpr int TS = 64;          // rows and columns of a tile; also the width of the solver's block of vectors
-constexpr int KC = 16;          // K per LDS stage
-constexpr int LS = 80;          // doubles between two k of a staged tile (as in pesto_cluster.hip: the 4 k of one MFMA step fall on both halves of the banks)
-constexpr int HS = TS + 1;      // doubles between two rows of a 64 x 64 image in LDS
+constexpr int TS = MT;          // rows and columns of a tile (pesto_mma64.h); also the width of the solver's block of vectors
 constexpr int MG = 16;          // k_dyn_mean: coordinates per workgroup, and frame groups
 constexpr int ROUNDS = 4;       // solver iterations enqueued between two reads of the done flag
 constexpr double DROP = 1e-13;  // orthonormalisation: a direction whose Gram eigenvalue is below DROP x the largest is zeroed (the Gram
@@ -44,8 +42,6 @@ constexpr double DROP = 1e-13;  // orthonormalisation: a direction whose Gram ei
 constexpr double JTOL = 64 * 2.220446049250313e-16;      // k_dyn_jacobi: two columns count as orthogonal at |a_p . a_q| <= JTOL |a_p| |a_q|: the
                                 // rounding of that 64-term dot product itself is some 8 eps of |a_p| |a_q|, so a tighter test rotates on noise and never ends
 constexpr double RANK_TOL = 1e-12;   // a Ritz value at or below RANK_TOL x the largest is a null direction
-
-using f64x4 = __attribute__((ext_vector_type(4))) double;
 
 struct DynState {
     double total;               // tr C
@@ -119,14 +115,14 @@ struct Mma {
 };
 
 // operand (k = frame, row = coordinate base + ..): one float4 of a frame per thread, centred; mu: the thread's four means
-__device__ __forceinline__ void load_dcols(const Mma& a, int base, const double* mu, int k0, int kend, double* r) {
+__device__ __forceinline__ void load_dcols(const Mma& a, int base, const double* mu, int k0, int kend, f64x4& r) {
     const int f = k0 + (threadIdx.x >> 4);
     if (f >= kend) { r[0] = r[1] = r[2] = r[3] = 0.0; return; }          // the K tail: zero rows of d
     const float4 x = ((const float4*)(a.Xp + (size_t)f * a.mp + base))[threadIdx.x & 15];
     r[0] = (double)x.x - mu[0]; r[1] = (double)x.y - mu[1]; r[2] = (double)x.z - mu[2]; r[3] = (double)x.w - mu[3];
 }
 // operand (k = coordinate, row = frame f0 + ..): one float4 of four consecutive coordinates per thread, centred
-__device__ __forceinline__ void load_drows(const Mma& a, int f0, int k0, int kend, double* r) {
+__device__ __forceinline__ void load_drows(const Mma& a, int f0, int k0, int kend, f64x4& r) {
     const int f = f0 + (threadIdx.x >> 2), j = k0 + 4 * (threadIdx.x & 3);
     if (f >= a.F || j >= kend) { r[0] = r[1] = r[2] = r[3] = 0.0; return; }
     const float4 x = *(const float4*)(a.Xp + (size_t)f * a.mp + j);
@@ -134,27 +130,22 @@ __device__ __forceinline__ void load_drows(const Mma& a, int f0, int k0, int ken
     r[0] = (double)x.x - mu[0]; r[1] = (double)x.y - mu[1]; r[2] = (double)x.z - mu[2]; r[3] = (double)x.w - mu[3];
 }
 // operand (k = row of M, column): four doubles of a row of a [K][64] matrix per thread
-__device__ __forceinline__ void load_mat(const double* __restrict__ M, int k0, int kend, double* r) {
+__device__ __forceinline__ void load_mat(const double* __restrict__ M, int k0, int kend, f64x4& r) {
     const int k = k0 + (threadIdx.x >> 4);
     if (k >= kend) { r[0] = r[1] = r[2] = r[3] = 0.0; return; }
     const double* p = M + (size_t)k * TS + 4 * (threadIdx.x & 15);
     r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3];
 }
-__device__ __forceinline__ void store_kmajor(double* S, const double* r) {
-    double* d = S + (threadIdx.x >> 4) * LS + 4 * (threadIdx.x & 15);
-    d[0] = r[0]; d[1] = r[1]; d[2] = r[2]; d[3] = r[3];
-}
-__device__ __forceinline__ void store_rowmajor(double* S, const double* r) {
+// load_drows' four values (rows 4 (tid % 4) .., column tid / 4) into a k-major stage
+__device__ __forceinline__ void store_rowmajor(double* S, const f64x4& r) {
     double* d = S + (4 * (threadIdx.x & 3)) * LS + (threadIdx.x >> 2);
     d[0] = r[0]; d[LS] = r[1]; d[2 * LS] = r[2]; d[3 * LS] = r[3];
 }
 
-// Workgroup (tile, split): sum over k in [split chunk, min(K, (split + 1) chunk)) of A[k][row] B[k][col]. Wave w owns the rows 16 w ..
-// 16 w + 15 against all 64 columns (four 16 x 16 accumulators).
+// Workgroup (tile, split): sum over k in [split chunk, min(K, (split + 1) chunk)) of A[k][row] B[k][col], one tile of pesto_mma64.h.
 template <int MODE>
 __global__ __launch_bounds__(NT) void k_dyn_mma(Mma a) {
-    __shared__ double lds[TS * HS];             // the staged operands (2 x KC x LS doubles), then (GRAM) the accumulator image
-    static_assert(2 * KC * LS <= TS * HS, "the staged operands must fit the accumulator image");
+    __shared__ double lds[MMA64_LDS];           // the staged operands, then (GRAM) the accumulator image
     if (a.st && a.st->done) return;
     int ti = blockIdx.x, tj = 0;
     if (MODE == M_GRAM) {
@@ -162,54 +153,23 @@ __global__ __launch_bounds__(NT) void k_dyn_mma(Mma a) {
         if (tj < ti) return;
     }
     const int kbeg = blockIdx.y * a.chunk, kend = min(a.K, kbeg + a.chunk);
-    double* As = lds;
-    double* Bs = lds + KC * LS;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
     double mua[4] = {0.0, 0.0, 0.0, 0.0}, mub[4] = {0.0, 0.0, 0.0, 0.0};
     if (MODE == M_GRAM || MODE == M_DTZ)
         for (int i = 0; i < 4; ++i) mua[i] = a.mean[TS * ti + 4 * (threadIdx.x & 15) + i];
     if (MODE == M_GRAM)
         for (int i = 0; i < 4; ++i) mub[i] = a.mean[TS * tj + 4 * (threadIdx.x & 15) + i];
-    auto load = [&](int k0, double* ra, double* rb) {
+    auto load = [&](int k0, f64x4& ra, f64x4& rb) {
         if (MODE == M_GRAM) { load_dcols(a, TS * ti, mua, k0, kend, ra); load_dcols(a, TS * tj, mub, k0, kend, rb); }
         if (MODE == M_DTZ) { load_dcols(a, TS * ti, mua, k0, kend, ra); load_mat(a.B, k0, kend, rb); }
         if (MODE == M_DQ) { load_drows(a, TS * ti, k0, kend, ra); load_mat(a.B, k0, kend, rb); }
         if (MODE == M_QTY) { load_mat(a.A, k0, kend, ra); load_mat(a.B, k0, kend, rb); }
     };
+    auto store = [](double* As, const f64x4& ra) { MODE == M_DQ ? store_rowmajor(As, ra) : store_kmajor(As, ra); };
     f64x4 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = f64x4{0.0, 0.0, 0.0, 0.0};
-    double ra[4], rb[4];
-    load(kbeg, ra, rb);
-    for (int k0 = kbeg; k0 < kend; k0 += KC) {
-        __syncthreads();
-        if (MODE == M_DQ) store_rowmajor(As, ra); else store_kmajor(As, ra);
-        store_kmajor(Bs, rb);
-        __syncthreads();
-        if (k0 + KC < kend) load(k0 + KC, ra, rb);
-#pragma unroll
-        for (int s = 0; s < KC / 4; ++s) {          // a stage beyond kend holds zeros
-            const double* a_row = As + (4 * s + lk) * LS;
-            const double* b_row = Bs + (4 * s + lk) * LS;
-            const double av = a_row[16 * w + lr];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b_row[16 * c + lr], acc[c], 0, 0, 0);
-        }
-    }
-    // C/D of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 reg
-    if (MODE != M_GRAM) {
-        double* o = a.out + ((size_t)blockIdx.y * gridDim.x + ti) * TS * TS;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[(16 * w + lk + 4 * r) * TS + 16 * c + lr] = acc[c][r];
-        return;
-    }
+    mma64_loop<f64x4, false>(lds, kbeg, kend, load, store, acc);            // every stage in full: one beyond kend holds zeros
+    if (MODE != M_GRAM) { mma64_store(acc, a.out + ((size_t)blockIdx.y * gridDim.x + ti) * TS * TS, TS, 1.0); return; }
     __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lds[(16 * w + lk + 4 * r) * HS + 16 * c + lr] = acc[c][r] * a.fac;
+    mma64_store(acc, lds, HS, a.fac);
     __syncthreads();
     const int I = TS * ti, J = TS * tj;
     for (int e = threadIdx.x; e < TS * TS; e += NT) {
@@ -293,9 +253,8 @@ __global__ __launch_bounds__(NT) void k_dyn_jacobi(const double* __restrict__ T,
             }
             for (int o = 1; o < 8; o <<= 1) { alpha += __shfl_xor(alpha, o); beta += __shfl_xor(beta, o); gamma += __shfl_xor(gamma, o); }
             if (fabs(gamma) > JTOL * sqrt(alpha * beta)) {
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+                double c, s;
+                jacobi_angle(alpha, beta, gamma, c, s);
                 for (int r = sub; r < TS; r += 8) {
                     const double ap = A[r * HS + p], aq = A[r * HS + q], vp = V[r * HS + p], vq = V[r * HS + q];
                     A[r * HS + p] = c * ap - s * aq; A[r * HS + q] = s * ap + c * aq;

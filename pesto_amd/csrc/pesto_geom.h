@@ -1,7 +1,7 @@
 // pesto_geom.h - the geometry the analysis groups share (pesto_hbonds.hip, pesto_lddt.hip, pesto_cluster.hip, pesto_peaks.hip,
 // pesto_dynamics.hip, and pesto_trajectory.hip, pesto_docking.hip and pesto_dockq.hip through pesto_fit.h): the float32 squared distance
 // of NumPy and torch, the host's derivation of squared-distance thresholds from it, the workgroup sum in double and the rotation of a
-// Kabsch superposition (kabsch_rotation: called by the one superposition fit, pesto_fit.h; kabsch_trace: pesto_cluster.hip). Also one
+// Kabsch superposition (kabsch_rotation: the one superposition fit, pesto_fit.h; kabsch_trace: pesto_cluster.hip; jacobi_angle). Also one
 // edge of the model's geometry (r, |r|, the fix-up) for the backward of the geometry pass (pesto_train.hip).
 //
 // Everything sits in an anonymous namespace (one copy per translation unit, like pesto_call.h).
@@ -52,6 +52,13 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 }
 
 
+// c, s of the Jacobi rotation that makes two columns orthogonal (alpha = |a_p|^2, beta = |a_q|^2, gamma = a_p . a_q != 0); also k_dyn_jacobi's
+__device__ __forceinline__ void jacobi_angle(double alpha, double beta, double gamma, double& c, double& s) {
+    const double zeta = (beta - alpha) / (2.0 * gamma);
+    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    c = 1.0 / sqrt(1.0 + t * t); s = c * t;
+}
+
 // R of the 3x3 covariance H = (ref - t_ref)^T (xyz - t) = U S V^T: R = V diag(1, 1, det(U) det(V)) U^T, by one-sided Jacobi in double
 // (columns of H V rotated until orthogonal: H V = U S). With U2' = U0 x U1 and the true U2 = +-U2', the sign cancels against det(U):
 // R = V0 U0^T + V1 U1^T + det(V) V2 U2'^T, columns ordered by singular value, so the smallest one is never divided by.
@@ -67,9 +74,8 @@ __device__ void kabsch_rotation(const double* H, double* R) {
                 for (int k = 0; k < 3; ++k) { alpha += A[k][p] * A[k][p]; beta += A[k][q] * A[k][q]; gamma += A[k][p] * A[k][q]; }
                 if (fabs(gamma) <= 1e-15 * sqrt(alpha * beta)) continue;     // orthogonal to a few units of double rounding (also gamma == 0)
                 rotated = true;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+                double c, s;
+                jacobi_angle(alpha, beta, gamma, c, s);
                 for (int k = 0; k < 3; ++k) {
                     const double ap = A[k][p], aq = A[k][q], vp = V[k][p], vq = V[k][q];
                     A[k][p] = c * ap - s * aq; A[k][q] = s * ap + c * aq;
@@ -133,9 +139,8 @@ __device__ double kabsch_trace(const double* H) {
                 for (int k = 0; k < 3; ++k) { alpha += A[k][p] * A[k][p]; beta += A[k][q] * A[k][q]; gamma += A[k][p] * A[k][q]; }
                 if (fabs(gamma) <= 1e-15 * sqrt(alpha * beta)) continue;
                 rotated = true;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+                double c, s;
+                jacobi_angle(alpha, beta, gamma, c, s);
                 for (int k = 0; k < 3; ++k) {
                     const double ap = A[k][p], aq = A[k][q];
                     A[k][p] = c * ap - s * aq; A[k][q] = s * ap + c * aq;

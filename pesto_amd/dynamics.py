@@ -32,8 +32,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib
-from .clustering import _sel
-from .trajectory import _model_of, _xyz
+from .trajectory import _model_of, _selection, _xyz
 
 MAX_FRAMES = 2 ** 24        # PESTO_DYNAMICS_MAX_FRAMES
 MAX_ATOMS = 2 ** 24         # PESTO_DYNAMICS_MAX_ATOMS
@@ -66,7 +65,7 @@ def _check(xyz, sel, scale, ddof=None, cov=False):
     F, N = int(a.shape[0]), int(a.shape[1])
     if F > MAX_FRAMES or N > MAX_ATOMS:
         raise ValueError(f"at most 2**24 frames and 2**24 atoms, got {F} and {N}")
-    s, n = _sel(sel, N)
+    s, n = _selection(sel, N, "sel", least=1)
     sc = float(scale)
     if not (np.isfinite(sc) and abs(sc) <= F32_MAX):
         raise ValueError(f"scale must be finite, got {scale!r}")

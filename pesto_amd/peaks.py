@@ -43,8 +43,8 @@ from typing import Any, NamedTuple
 import numpy as np
 
 from . import _lib
-from .clustering import MAX_FRAMES, _sel
-from .trajectory import _model_of
+from .clustering import MAX_FRAMES
+from .trajectory import _model_of, _selection
 
 MAX_POINTS = 1 << 17        # PESTO_PEAKS_MAX_POINTS: n over points
 MAX_CLUSTERS = 1024         # PESTO_PEAKS_MAX_CLUSTERS: n_clusters
@@ -174,7 +174,7 @@ def _check_source(X, D, idx):
         s, n = None, F
     else:
         try:
-            s, n = _sel(idx, F)
+            s, n = _selection(idx, F, "sel", least=1)
         except ValueError as err:
             raise ValueError(str(err).replace("sel", "idx").replace("atoms", "rows").replace("atom", "row")) from None
     if X is not None and n > MAX_POINTS:

@@ -276,7 +276,8 @@ def fnat(maps_ref, maps, model=None):
     return nat / tot[0]
 
 
-def _selection(sel, n_atoms, name):
+def _selection(sel, n_atoms, name, least=0):
+    """(int32 indices or None for all atoms, their number) of a selection given as indices or as a mask; least > 0: it must hold that many."""
     if sel is None:
         return None, n_atoms
     s = _lib.host(sel).reshape(-1)
@@ -286,6 +287,8 @@ def _selection(sel, n_atoms, name):
         s = np.nonzero(s)[0]
     if not np.issubdtype(s.dtype, np.integer):
         raise ValueError(f"{name} must hold atom indices or be a mask, got {s.dtype}")
+    if least and not least <= s.size <= n_atoms:
+        raise ValueError(f"{name} must select {least} to {n_atoms} atoms, got {s.size}")
     if s.size and (s.min() < 0 or s.max() >= n_atoms):
         raise ValueError(f"{name}: atom indices must lie in 0 .. {n_atoms - 1}")
     return s.astype(np.int32), int(s.size)

@@ -70,7 +70,7 @@ def frames(F, n, seed):
 
 def source_hash():
     h = hashlib.sha256()
-    for rel in ("pesto_amd/csrc/pesto_cluster.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/clustering.py", "profiles/bench_clustering.py"):
+    for rel in ("pesto_amd/csrc/pesto_cluster.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/csrc/pesto_mma64.h", "pesto_amd/clustering.py", "profiles/bench_clustering.py"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 

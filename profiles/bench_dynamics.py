@@ -97,7 +97,7 @@ def gram_flops(F, n):
 
 def source_hash():
     h = hashlib.sha256()
-    for rel in ("pesto_amd/csrc/pesto_dynamics.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/dynamics.py", "profiles/bench_dynamics.py"):
+    for rel in ("pesto_amd/csrc/pesto_dynamics.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/csrc/pesto_mma64.h", "pesto_amd/dynamics.py", "profiles/bench_dynamics.py"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 

@@ -18,7 +18,7 @@ ON = pytest.mark.parametrize("on_device", [False, True], ids=["host", "device"])
 # (Fa, Fb; Fb None: the self form): every residue of the 4-frame MFMA rows and of the 16-frame tile, one and several tiles a side
 SWEEP_PAIRS = [(1, 1), (1, 65), (65, 1), (3, 4), (4, 3), (5, 15), (15, 16), (16, 17), (17, 5), (63, 64), (64, 65), (65, 63), (16, 16), (4, 64),
                (64, 4), (3, 63), (1, None), (5, None), (17, None), (64, None), (65, None)]
-SWEEP_ATOMS = [1, 2, 3, 4, 5, 7, 8, 63, 64, 65, 257]
+SWEEP_ATOMS = [1, 2, 3, 4, 5, 7, 8, 15, 16, 17, 63, 64, 65, 257]
 CLUSTER_FRAMES = [1, 2, 63, 64, 65, 129, 200]
 
 

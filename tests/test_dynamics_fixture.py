@@ -388,5 +388,7 @@ def test_exports_header_and_abi():
     assert re.search(r"PESTO_DYNAMICS_MAX_COMPONENTS = (\d+)", hdr).group(1) == str(dy.MAX_COMPONENTS)
     assert "pesto_dynamics.hip" in build.SOURCES
     src = open(os.path.join(ROOT, "pesto_amd", "csrc", "pesto_dynamics.hip")).read()
-    assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in src and "atomicAdd" not in src
+    tile = open(os.path.join(ROOT, "pesto_amd", "csrc", "pesto_mma64.h")).read()           # the f64 MFMA tile k_dyn_mma is built on
+    assert '#include "pesto_mma64.h"' in src and "mma64_loop<" in src and "_mfma_f64_" in tile
+    assert "atomicAdd" not in src and "atomicAdd" not in tile
     assert float(re.search(r"RANK_TOL = ([0-9.e+-]+);", src).group(1)) == RANK_TOL
