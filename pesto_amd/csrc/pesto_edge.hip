@@ -392,6 +392,18 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : WPB / 4) void k_edge(const
 #include "pesto_edge_node_waves.inc"
       }
     }
+    // PFI (node-wave mode): the edge rows (neighbour id, geometry) of the wave's NEXT work item are requested at the top of the current
+    // item and wait in five registers - what first_nb / first_geo above do for the first item of a launch. An item otherwise begins with a
+    // dependent round trip (rows -> LDS scratch -> first gathers) that the only other item wave of the SIMD hides badly. Not in rendezvous
+    // mode: its waves run the finish phase, which needs every register. Scheduling only: the same rows reach the scratch, the same bits.
+    // The two loads are the oldest of the wave while they fly, so no later s_waitcnt vmcnt(N) waits longer for them; no scratch in any
+    // instantiation. Same box, interleaved kernel traces (profiles/r07_item_prefetch_ab.txt): nn = 8 / 16 / 32 51.8 -> 51.5, 81.4 -> 80.1,
+    // 143.1 -> 139.7 us per launch on a quiet box (the untouched nn = 64 kernel moved by -0.8 % in the same runs); inside the spread on a
+    // noisier one.
+    constexpr bool PFI = NODEW;
+    int pf_nb = 0;
+    f32x4 pf_geo = f32x4{0, 0, 0, 0};
+    (void)pf_nb; (void)pf_geo;
     for (int it_start = xcd * chunk; it_start < w_end; it_start += nbx * NE * SUBS) {
       // the lane-derived values of the work loop (indices, LDS addresses, masks) are re-derived per iteration from an opaque copy of the
       // thread index: as loop invariants they would stay in registers across the finish / prepare phase below, which needs them for
@@ -436,14 +448,31 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : WPB / 4) void k_edge(const
             const int a = lane / NN, c = lane % NN, i = c0 + a;
             const bool valid = i < N1 && lane < 16 * TI;
             const unsigned src = (unsigned)min(i, N1 - 1) * KMAX + c;       // unconditional loads, select afterwards
-            const int nbv = __builtin_bit_cast(int, bufld1(make_rsrc(ids_s), (int)(src * 4u)));
-            const f32x4 gg4 = bufld4(make_rsrc(geo), (int)(src * 16u));
+            const int nbv = PFI ? pf_nb : __builtin_bit_cast(int, bufld1(make_rsrc(ids_s), (int)(src * 4u)));
+            const f32x4 gg4 = PFI ? pf_geo : bufld4(make_rsrc(geo), (int)(src * 16u));
             const float4 gg = float4{gg4[0], gg4[1], gg4[2], gg4[3]};
             ws.nb[lane] = valid ? nbv : 0;
             ws.geo[0][lane] = valid ? gg.x : 0.f; ws.geo[1][lane] = valid ? gg.y : 0.f; ws.geo[2][lane] = valid ? gg.z : 0.f;
             ws.geo[3][lane] = valid ? gg.w : 0.f; ws.geo[4][lane] = 1.0f;
         }
         __builtin_amdgcn_wave_barrier();
+        if constexpr (PFI) {
+            // the wave's NEXT item, by the loop's own arithmetic (scalar): the next sub-item of this iteration, else the first one of the
+            // next iteration with that iteration's own tail / base. Every item of a full iteration exists and a tail iteration is the last
+            // one, so the items a wave processes are consecutive in this order: the item that finds these registers is the one they are for.
+            const int wave_s = __builtin_amdgcn_readfirstlane(wave), round = nbx * NE * SUBS;
+            int nwork = w_end;                                                  // (no successor: nothing is requested)
+            if (sub + 1 < SUBS) nwork = base + (sub + 1) * sstride + wave_s;
+            else if (!tail && it_start + round < w_end) {
+                const int it2 = it_start + round;
+                nwork = it2 + jb * NE * (w_end - it2 < round ? 1 : SUBS) + wave_s;
+            }
+            if (nwork < w_end) {
+                const unsigned src = (unsigned)min(nwork * A + lane / NN, N1 - 1) * KMAX + lane % NN;
+                pf_nb = __builtin_bit_cast(int, bufld1(make_rsrc(ids_s), (int)(src * 4u)));
+                pf_geo = bufld4(make_rsrc(geo), (int)(src * 16u));
+            }
+        }
 
         // ------------------------------------------------------------------ pass 1: keys -> logits (eqkm, epkm)
         constexpr bool ONEP = TI == 1 && !PF && HY;      // one-tile items: see l1_issue_ac

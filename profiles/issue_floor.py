@@ -86,7 +86,7 @@ def main():
         tf = json.load(open(sys.argv[3]))
         tf["issue_floor"] = {"per_nn": summary, "how": "profiles/issue_floor.py: dynamic instruction classes of a launch (rocprofv3 --pmc, profiles/pmc_classes.sh) x "
                              "the micro-benchmark price list, at the clock of the same dispatch (GRBM_GUI_ACTIVE / 8 XCDs / duration), against "
-                             "the launch time by HIP events in the same gpurun call"}
+                             "the launch time by HIP events in the same call"}
         json.dump(tf, open(sys.argv[3], "w"), indent=1)
     print()
     for (nn, ne) in sorted(res):

@@ -25,6 +25,6 @@ for row in csv.DictReader(open(stats)):
     elif "k_node16" in row["Name"]:
         tr["pesto::k_node16"] = {"calls": int(row["Calls"]), "avg_ns": float(row["AverageNs"])}
 t["rocprof_kernel_trace"] = {"kernels": tr, "how": "rocprofv3 --kernel-trace --stats of python bench.py --full --steps 20 --warmup 5 --precision f16_split "
-                                                    "(the same gpurun call as the PMC passes; the profiler adds ~5 % to a launch)"}
+                                                    "(the same call as the PMC passes; the profiler adds ~5 % to a launch)"}
 json.dump(t, open(tpath, "w"), indent=1)
 PY
