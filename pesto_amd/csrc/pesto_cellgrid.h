@@ -1,5 +1,5 @@
 // pesto_cellgrid.h - the float32 uniform cell grid of the contact searches (interface labels, pesto_eval.hip; dataset contacts,
-// pesto_contacts.hip), and the small device helpers the analysis groups share (struct_of, the one-workgroup scan, torch.norm's distance).
+// pesto_contacts.hip) and torch.norm's distance; pesto_lddt.hip builds its reference list on the same grid. The scans: pesto_scan.h.
 //
 // Both searches replace the reference's dense torch distance matrix per pair of subunits (locate_contacts / extract_all_contacts,
 // src/data_encoding.py:116-176): every atom pair of two subunits of one assembly with |x_a - x_b| < r_thr, the distance being the
@@ -14,14 +14,12 @@
 //     everybody, itself included, in every comparison.
 // Build: k_grid_setup -> k_grid_count -> k_grid_scan -> k_grid_scatter, four launches; the users differ in what they check per atom in
 // the count pass and in the payload they scatter beside the coordinates, both functors.
-// (pesto_sasa.hip includes this header for struct_of and block_scan_exclusive only: its grid is another one, in double and per frame;
-// pesto_dssp.hip likewise: it has no grid; pesto_docking.hip and pesto_hbonds.hip take the list protocol's scans, k_frame_scan and
-// k_list_offsets; pesto_rank.hip the one-workgroup scan and k_list_offsets;
-// pesto_surface.hip struct_of and k_list_offsets.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+
+#include "pesto_scan.h"
 
 namespace pesto {
 
@@ -32,13 +30,6 @@ struct CellGrid { float minx, miny, minz, inv_h; int nx, ny, nz, base; };
 
 // cells of the assemblies before s (off_s atoms), and of a whole batch for (n_total, n_struct): 2 N_s + 64 and the total slot each
 __host__ __device__ inline size_t cells_before(size_t off_s, size_t s) { return 2 * off_s + 65 * s; }
-
-// the range [offsets[k], offsets[k + 1]) of offsets[0 .. n] that holds i (offsets[0] <= i)
-__device__ __forceinline__ int struct_of(int i, int n, const int* __restrict__ offsets) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
-}
 
 __device__ __forceinline__ void cell3(const CellGrid& g, float x, float y, float z, int& cx, int& cy, int& cz) {
     cx = min(g.nx - 1, max(0, (int)((x - g.minx) * g.inv_h)));
@@ -51,75 +42,6 @@ __device__ __forceinline__ void cell3(const CellGrid& g, float x, float y, float
 __device__ __forceinline__ float dist(float4 a, float4 b) {
     const float rx = b.x - a.x, ry = b.y - a.y, rz = b.z - a.z;
     return sqrtf(__fmaf_rn(rz, rz, __fmaf_rn(ry, ry, __fmul_rn(rx, rx))));
-}
-
-// exclusive scan in place of data[0, len) by one workgroup of NT threads (all of them call); with COPY, `copy` receives the result too
-// (a compile-time choice: the loop is a chain of dependent loads, a test per element shows). Returns the total in every thread.
-template <int NT, bool COPY>
-__device__ __forceinline__ int block_scan_exclusive(int* __restrict__ data, int len, int* __restrict__ copy = nullptr) {
-    __shared__ int part[NT];
-    const int per = (len + NT - 1) / NT;
-    const int c0 = min(len, (int)threadIdx.x * per), c1 = min(len, c0 + per);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += data[c];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < NT; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - sum;
-    for (int c = c0; c < c1; ++c) {
-        const int n = data[c];
-        data[c] = run;
-        if (COPY) copy[c] = run;
-        run += n;
-    }
-    return part[NT - 1];
-}
-
-// ---- the list protocol of pesto_docking.hip and pesto_hbonds.hip: count -> scan per frame -> 64-bit offsets -> emit
-constexpr int LIST_SCAN_NT = 1024;      // threads of the one workgroup that scans the frames' totals
-
-// the device counters of one call
-struct ListState {
-    long long K;      // list entries over all frames
-    int fits;         // K <= capacity: the emit pass runs
-    int err;          // error bits of the call's own index checks
-};
-
-// one workgroup per frame: the frame's n counts scanned in place (exclusive), their total to ftot[f]
-template <int NT>
-__global__ __launch_bounds__(NT) void k_frame_scan(int n, int* __restrict__ cnt, int* __restrict__ ftot) {
-    const int total = block_scan_exclusive<NT, false>(cnt + (size_t)blockIdx.x * n, n);
-    if (threadIdx.x == 0) ftot[blockIdx.x] = total;
-}
-
-// one workgroup: off[0 .. F] = exclusive scan of the frames' totals in 64 bits; K and whether it fits the capacity
-__global__ __launch_bounds__(LIST_SCAN_NT) void k_list_offsets(int F, const int* __restrict__ ftot, long long* __restrict__ off, long long cap,
-                                                               ListState* __restrict__ st) {
-    __shared__ long long part[LIST_SCAN_NT];
-    const int per = (F + LIST_SCAN_NT - 1) / LIST_SCAN_NT;
-    const int c0 = min(F, (int)threadIdx.x * per), c1 = min(F, c0 + per);
-    long long sum = 0;
-    for (int c = c0; c < c1; ++c) sum += ftot[c];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 1; o < LIST_SCAN_NT; o <<= 1) {
-        const long long v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    long long run = part[threadIdx.x] - sum;
-    for (int c = c0; c < c1; ++c) { off[c] = run; run += ftot[c]; }
-    if (threadIdx.x == LIST_SCAN_NT - 1) {
-        off[F] = part[LIST_SCAN_NT - 1];
-        st->K = part[LIST_SCAN_NT - 1];
-        st->fits = part[LIST_SCAN_NT - 1] <= cap ? 1 : 0;
-    }
 }
 
 // one workgroup per assembly: bounding box -> cell size and counts, cleared cell counters

@@ -15,7 +15,7 @@
 #include <cmath>
 
 #include "pesto_call.h"
-#include "pesto_cellgrid.h"      // (for the list protocol's scans only: there is no cell grid here)
+#include "pesto_scan.h"
 #include "pesto_fit.h"           // (and pesto_geom.h through it)
 
 namespace pesto {
@@ -25,9 +25,9 @@ namespace {
 constexpr int NT = 256;                 // threads per workgroup of every kernel here
 constexpr int FC_ROWS = 8;              // frame contacts: atoms of A per wave (their partners' coordinates are loaded once for all of them)
 constexpr int FC_TILE = FC_ROWS * NT / 64;      // ... and per workgroup
-constexpr int SCAN_NT = LIST_SCAN_NT;   // threads of the one workgroup that scans the frames' totals (k_list_offsets, pesto_cellgrid.h)
+constexpr int SCAN_NT = LIST_SCAN_NT;   // threads of the one workgroup that scans the frames' totals (k_list_offsets, pesto_scan.h)
 
-// the device counters of one call (pesto_cellgrid.h); err bit 0: an atom index outside its side; bit 1: a residue row outside 0 .. R - 1
+// the device counters of one call (pesto_scan.h); err bit 0: an atom index outside its side; bit 1: a residue row outside 0 .. R - 1
 using DkState = ListState;
 
 // ------------------------------------------------------------------------------------------------ frame contacts
@@ -83,20 +83,13 @@ __global__ __launch_bounds__(NT) void k_fc_pairs(int Na, int Nb, int tiles, cons
             if (i0 + r < Na) cnt[f * (size_t)Na + i0 + r] = n[r];
 }
 
-// (the per-frame scan k_frame_scan and the 64-bit offsets k_list_offsets: pesto_cellgrid.h)
+// (the per-frame scan k_frame_scan and the 64-bit offsets k_list_offsets: pesto_scan.h)
 
 // ------------------------------------------------------------------------------------------------ residue contacts
 // replaces: atoms_to_residue_contacts (trajectory_utils.py:233-264; np.unique and a Python loop per frame and residue pair). Frame f owns
 // W words of a bit map over (ra, rb), bit ra * Rb + rb: mark sets the bit of every contact, the set bits in index order are the residue
 // pairs in lexicographic order (count -> scan -> emit, as above), and every contact lowers its pair's minimum - an unsigned atomicMin over
 // the bits of the non-negative float d, which no order of arrival changes.
-
-// the frame that owns list entry k: off[f] <= k < off[f + 1]
-__device__ __forceinline__ int frame_of(long long k, int F, const long long* __restrict__ off) {
-    int lo = 0, hi = F;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= k) lo = mid; else hi = mid; }
-    return lo;
-}
 
 // the word and bit of contact k, false (and an error bit) for an index outside its range
 __device__ __forceinline__ bool contact_bit(long long k, int F, int Na, int Nb, int Ra, int Rb, int W, const long long* __restrict__ off,
@@ -107,7 +100,7 @@ __device__ __forceinline__ bool contact_bit(long long k, int F, int Na, int Nb, 
     const int ra = res_a[i], rb = res_b[j];
     if (ra < 0 || ra >= Ra || rb < 0 || rb >= Rb) { atomicOr(&st->err, 2); return false; }
     const long long b = (long long)ra * Rb + rb;
-    word = (size_t)frame_of(k, F, off) * W + (size_t)(b >> 5);
+    word = (size_t)struct_of(k, F, off) * W + (size_t)(b >> 5);
     bit = (int)(b & 31);
     return true;
 }

@@ -34,7 +34,7 @@
 #include <vector>
 
 #include "pesto_call.h"
-#include "pesto_cellgrid.h"      // struct_of and the one-workgroup scan only
+#include "pesto_scan.h"
 
 #pragma clang fp contract(off)
 

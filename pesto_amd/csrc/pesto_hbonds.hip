@@ -9,7 +9,7 @@
 // coordinates, without acos or root: u = D - H, v = A - H, c = (ux*vx + uy*vy) + uz*vz, uu and vv likewise, bonded iff
 // c < 0 && c*c > k * (uu*vv) with k = cos^2(angle), every operation rounded as written (hb_angle: no contraction). NaN, uu = 0 and vv = 0
 // fail it (c < 0 is false).
-// The frame lists come out of count -> per-frame scan -> 64-bit offsets -> emit (the list protocol of pesto_cellgrid.h); the occupancy
+// The frame lists come out of count -> per-frame scan -> 64-bit offsets -> emit (the list protocol of pesto_scan.h); the occupancy
 // lists out of the same protocol with a donor pair in the place of a frame. Tiled brute force, no cell grid. Nothing of size [P, A] is
 // stored: the frame lists keep one count per (frame, donor pair), the occupancy one per (donor pair, 64 acceptors).
 // Unwrapping sums every molecule's centre of mass in double in a fixed order and picks the first of the 27 images nearest to molecule 0.
@@ -17,7 +17,7 @@
 #include <cmath>
 
 #include "pesto_call.h"
-#include "pesto_cellgrid.h"      // (for the list protocol's scans only: there is no cell grid here)
+#include "pesto_scan.h"
 #include "pesto_geom.h"
 
 namespace pesto {

@@ -6,9 +6,7 @@
 // one 64-bit key
 //     col << 33 | desc(p) << 1 | y
 // desc being the order-preserving map of the float's bits, complemented (larger scores first), -0.0 canonicalised to +0.0. All columns are
-// sorted at once by one LSD radix sort: 8-bit digits, per pass a histogram per workgroup tile, one scan of the [digit][tile] counters and
-// a scatter that is stable within the pass (ranks by __ballot per wave, wave offsets through LDS); the keys are double-buffered and a
-// pass whose counters show one occupied bucket moves nothing (the buffers' roles are device state, RankState.src). The label rides in
+// sorted at once by the LSD radix sort of pesto_radix.h, from bit 0 up (the sorted keys are where radix_sorted() says). The label rides in
 // the low bit: there is no payload, and the order inside a group of equal scores is irrelevant because every output is a per-group total.
 //
 // After the sort everything is integer arithmetic. Column col of segment s starts at res_offsets[s] * C + c * R_s. The group ends (desc
@@ -17,31 +15,26 @@
 // which are sklearn's _binary_clf_curve. They are kept as two compact arrays over all group ends (pt_pos, pt_tp) with the first point
 // and the y total before each column (col_pt0, col_y0); the scores, the curves and the histograms are read from those.
 //
-// The C entry points (include/pesto_hip.h) live here too, on the call plumbing of pesto_call.h and the list protocol of pesto_cellgrid.h.
+// The C entry points (include/pesto_hip.h) live here too, on the call plumbing of pesto_call.h and the list protocol of pesto_scan.h.
 #include <cmath>
 
 #include "pesto_call.h"
-#include "pesto_cellgrid.h"
+#include "pesto_radix.h"
 
 namespace pesto {
 
 namespace {
 
-constexpr int RK_NT = 256;                       // threads per workgroup of every kernel here but the scans
-constexpr int RK_ITEMS = 8;                      // keys per thread and radix pass
-constexpr int RK_TILE = PESTO_RANK_TILE;         // keys per workgroup and radix pass
-constexpr int RK_WAVES = RK_NT / 64;
-constexpr int RK_MAX_PASSES = 8;
-static_assert(RK_TILE == RK_NT * RK_ITEMS, "a tile is RK_ITEMS rounds of one key per thread");
+constexpr int RK_NT = RADIX_NT;                  // threads per workgroup of every kernel here but the scans
+constexpr int RK_TILE = PESTO_RANK_TILE;         // keys per workgroup of the kernels after the sort, which walk its tiles
+static_assert(RK_TILE == RADIX_TILE && RK_NT * RADIX_ITEMS == RK_TILE, "the tiles of the sort, RADIX_ITEMS keys per thread");
 
-typedef unsigned long long u64;
-
-// the device state of one call: the list protocol's counters (err bit 0: a non-finite p), which of the two key buffers pass k reads
-// (src[n_pass]: where the sorted keys are) and the passes that move nothing
+// the device state of one call: the list protocol's counters (err bit 0: a non-finite p), the number of keys (k_rank_keys writes it
+// for the sort, which reads its length on the device) and the sort's own state
 struct RankState {
     ListState ls;
-    int src[RK_MAX_PASSES + 1];
-    int skip[RK_MAX_PASSES];
+    int n;
+    RadixState rs;
 };
 
 __device__ __forceinline__ unsigned rk_desc(float v) {
@@ -64,95 +57,13 @@ __global__ __launch_bounds__(RK_NT) void k_rank_keys(long long n, int n_class, i
                                                      RankState* __restrict__ st) {
     const long long e = (long long)blockIdx.x * RK_NT + threadIdx.x;
     if (e >= n) return;
+    if (e == 0) st->n = (int)n;
     const int r = (int)(e / n_class), c = (int)(e - (long long)r * n_class);
     const int s = struct_of(r, n_struct, roff);
     const float v = p[e];
     if (!(fabsf(v) <= 3.402823466e38f)) atomicOr(&st->ls.err, 1);
     const u64 col = (u64)s * (u64)n_class + (u64)c;
     keys[e] = col << 33 | (u64)rk_desc(v) << 1 | (u64)(y[e] != 0);
-}
-
-// ------------------------------------------------------------------------------------------------ the radix passes
-// digit counts of tile blockIdx.x -> counters[digit * n_tiles + tile]
-__global__ __launch_bounds__(RK_NT) void k_radix_hist(long long n, int n_tiles, int pass, const u64* __restrict__ keys_a,
-                                                      const u64* __restrict__ keys_b, const RankState* __restrict__ st, int* __restrict__ counters) {
-    __shared__ int hist[256];
-    const u64* src = st->src[pass] ? keys_b : keys_a;
-    const int shift = 8 * pass;
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    const long long t0 = (long long)blockIdx.x * RK_TILE;
-#pragma unroll
-    for (int i = 0; i < RK_ITEMS; ++i) {
-        const long long j = t0 + i * RK_NT + threadIdx.x;
-        if (j < n) atomicAdd(&hist[(unsigned)(src[j] >> shift) & 255u], 1);
-    }
-    __syncthreads();
-    counters[(size_t)threadIdx.x * n_tiles + blockIdx.x] = hist[threadIdx.x];
-}
-
-// one workgroup: the counters scanned in place (digit-major, so tile t's keys of digit d start at counters[d * n_tiles + t]); a pass
-// with one occupied bucket is skipped and leaves the buffers' roles as they are
-__global__ __launch_bounds__(1024) void k_radix_scan(long long n, int n_tiles, int pass, int* __restrict__ counters, RankState* __restrict__ st) {
-    __shared__ int one;
-    if (threadIdx.x == 0) one = 0;
-    block_scan_exclusive<1024, false>(counters, 256 * n_tiles);
-    __syncthreads();
-    if (threadIdx.x < 256) {
-        const long long hi = threadIdx.x < 255 ? counters[((size_t)threadIdx.x + 1) * n_tiles] : n;
-        if (hi - counters[(size_t)threadIdx.x * n_tiles] == n) one = 1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        st->skip[pass] = one;
-        st->src[pass + 1] = one ? st->src[pass] : 1 - st->src[pass];
-    }
-}
-
-// the keys of tile blockIdx.x to their places, in their order within the tile (key i * RK_NT + t is the i-th round's t-th): per round
-// every wave matches equal digits with eight ballots (rank among the lanes before, count), the waves' counts meet in LDS
-__global__ __launch_bounds__(RK_NT) void k_radix_scatter(long long n, int n_tiles, int pass, u64* __restrict__ keys_a, u64* __restrict__ keys_b,
-                                                         const RankState* __restrict__ st, const int* __restrict__ counters) {
-    if (st->skip[pass]) return;
-    __shared__ int base[256];
-    __shared__ int wcnt[RK_WAVES][256];
-    const int from = st->src[pass];
-    const u64* src = from ? keys_b : keys_a;
-    u64* dst = from ? keys_a : keys_b;
-    const int shift = 8 * pass;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    base[threadIdx.x] = counters[(size_t)threadIdx.x * n_tiles + blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < RK_WAVES; ++k) wcnt[k][threadIdx.x] = 0;
-    __syncthreads();
-    const long long t0 = (long long)blockIdx.x * RK_TILE;
-    for (int i = 0; i < RK_ITEMS; ++i) {
-        const long long j = t0 + i * RK_NT + threadIdx.x;
-        const bool valid = j < n;
-        const u64 key = valid ? src[j] : 0;
-        const unsigned d = (unsigned)(key >> shift) & 255u;
-        u64 peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const u64 m = __ballot(valid && bit);
-            peers &= bit ? m : ~m;
-        }
-        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0) wcnt[w][d] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            long long pos = base[d] + rank;
-            for (int k = 0; k < w; ++k) pos += wcnt[k][d];
-            if (pos < n) dst[pos] = key;                           // (always, when the counters are this buffer's)
-        }
-        __syncthreads();
-        int add = 0;
-#pragma unroll
-        for (int k = 0; k < RK_WAVES; ++k) { add += wcnt[k][threadIdx.x]; wcnt[k][threadIdx.x] = 0; }
-        base[threadIdx.x] += add;
-        __syncthreads();
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ group ends and the scan of y
@@ -164,12 +75,12 @@ __device__ __forceinline__ bool rk_group_end(const u64* __restrict__ keys, long 
 __global__ __launch_bounds__(RK_NT) void k_rank_tile_sums(long long n, const u64* __restrict__ keys_a, const u64* __restrict__ keys_b, int n_pass,
                                                           const RankState* __restrict__ st, int* __restrict__ tile_y, int* __restrict__ tile_g) {
     __shared__ int sums[2];
-    const u64* keys = st->src[n_pass] ? keys_b : keys_a;
+    const u64* keys = radix_sorted(keys_a, keys_b, n_pass, &st->rs);
     if (threadIdx.x < 2) sums[threadIdx.x] = 0;
     __syncthreads();
-    const long long j0 = (long long)blockIdx.x * RK_TILE + threadIdx.x * RK_ITEMS;
+    const long long j0 = (long long)blockIdx.x * RK_TILE + threadIdx.x * RADIX_ITEMS;
     int ny = 0, ng = 0;
-    for (int i = 0; i < RK_ITEMS; ++i) {
+    for (int i = 0; i < RADIX_ITEMS; ++i) {
         const long long j = j0 + i;
         if (j >= n) break;
         ny += (int)(keys[j] & 1ull);
@@ -195,11 +106,11 @@ __global__ __launch_bounds__(RK_NT) void k_rank_points(long long n, const u64* _
                                                        const RankState* __restrict__ st, const int* __restrict__ tile_y, const int* __restrict__ tile_g,
                                                        long long n_col, int* __restrict__ pt_pos, int* __restrict__ pt_tp,
                                                        int* __restrict__ col_pt0, int* __restrict__ col_y0) {
-    __shared__ int packed[RK_NT];                  // positives << 16 | group ends of each thread's RK_ITEMS keys: both at most RK_TILE
-    const u64* keys = st->src[n_pass] ? keys_b : keys_a;
-    const long long j0 = (long long)blockIdx.x * RK_TILE + threadIdx.x * RK_ITEMS;
+    __shared__ int packed[RK_NT];                  // positives << 16 | group ends of each thread's RADIX_ITEMS keys: both at most RK_TILE
+    const u64* keys = radix_sorted(keys_a, keys_b, n_pass, &st->rs);
+    const long long j0 = (long long)blockIdx.x * RK_TILE + threadIdx.x * RADIX_ITEMS;
     int ny = 0, ng = 0;
-    for (int i = 0; i < RK_ITEMS; ++i) {
+    for (int i = 0; i < RADIX_ITEMS; ++i) {
         const long long j = j0 + i;
         if (j >= n) break;
         ny += (int)(keys[j] & 1ull);
@@ -210,7 +121,7 @@ __global__ __launch_bounds__(RK_NT) void k_rank_points(long long n, const u64* _
     block_scan_exclusive<RK_NT, false>(packed, RK_NT);
     const int before = packed[threadIdx.x];
     int ycum = tile_y[blockIdx.x] + (before >> 16), g = tile_g[blockIdx.x] + (before & 0xffff);
-    for (int i = 0; i < RK_ITEMS; ++i) {
+    for (int i = 0; i < RADIX_ITEMS; ++i) {
         const long long j = j0 + i;
         if (j >= n) break;
         const u64 key = keys[j];
@@ -273,7 +184,7 @@ __global__ __launch_bounds__(RK_NT) void k_rank_scores(int n_class, const int* _
     __shared__ u64 red_u[RK_NT];
     __shared__ double red_d[RK_NT];
     const long long col = blockIdx.x;
-    const Column v = rk_column(col, n_class, roff, st->src[n_pass] ? keys_b : keys_a, pt_pos, pt_tp, col_pt0, col_y0);
+    const Column v = rk_column(col, n_class, roff, radix_sorted(keys_a, keys_b, n_pass, &st->rs), pt_pos, pt_tp, col_pt0, col_y0);
     const long long P = v.tps(v.K - 1), N = v.rows - P;
     const long long per = ((long long)v.K + RK_NT - 1) / RK_NT;          // (64 bits: K may be within RK_NT of 2^31)
     const int k0 = (int)min((long long)v.K, (long long)threadIdx.x * per), k1 = (int)min((long long)v.K, k0 + per);
@@ -321,7 +232,7 @@ __global__ __launch_bounds__(RK_NT) void k_rank_curve(int n_class, int mode, con
     __shared__ int kept[RK_NT];
     if (EMIT && !st->ls.fits) return;
     const long long col = blockIdx.x;
-    const Column v = rk_column(col, n_class, roff, st->src[n_pass] ? keys_b : keys_a, pt_pos, pt_tp, col_pt0, col_y0);
+    const Column v = rk_column(col, n_class, roff, radix_sorted(keys_a, keys_b, n_pass, &st->rs), pt_pos, pt_tp, col_pt0, col_y0);
     const long long per = ((long long)v.K + RK_NT - 1) / RK_NT;          // (64 bits: K may be within RK_NT of 2^31)
     const int k0 = (int)min((long long)v.K, (long long)threadIdx.x * per), k1 = (int)min((long long)v.K, k0 + per);
     int mine = 0;
@@ -366,7 +277,7 @@ __global__ __launch_bounds__(RK_NT) void k_rank_histogram(long long n_cells, int
     if (i >= n_cells) return;
     const long long col = i / n_bins;
     const int b = (int)(i - col * n_bins);
-    const Column v = rk_column(col, n_class, roff, st->src[n_pass] ? keys_b : keys_a, pt_pos, pt_tp, col_pt0, col_y0);
+    const Column v = rk_column(col, n_class, roff, radix_sorted(keys_a, keys_b, n_pass, &st->rs), pt_pos, pt_tp, col_pt0, col_y0);
     long long r0, p0, r1, p1;
     rk_at_least(v, edges[b], false, r0, p0);
     rk_at_least(v, edges[b + 1], b == n_bins - 1, r1, p1);
@@ -412,7 +323,7 @@ void rank_declare(Buffers& bf, const int32_t* res_offsets, const uint8_t* y, con
     rk.iSt = bf.scratch(sizeof(RankState));
     rk.iKa = bf.scratch(n * 8);
     rk.iKb = bf.scratch(n * 8);
-    rk.iCnt = bf.scratch(256 * nt * 4);
+    rk.iCnt = bf.scratch(radix_counter_bytes(n));
     rk.iTy = bf.scratch(nt * 4);
     rk.iTg = bf.scratch(nt * 4);
     rk.iPos = bf.scratch(n * 4);
@@ -427,13 +338,7 @@ int rank_sort(Buffers& bf, const RankCall& rk, const char* what) {
     u64 *ka = bf.ptr<u64>(rk.iKa), *kb = bf.ptr<u64>(rk.iKb);
     hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)((rk.n + RK_NT - 1) / RK_NT)), dim3(RK_NT), 0, bf.stm, rk.n, rk.n_class, rk.n_struct,
                        bf.ptr<const int>(rk.iOff), bf.ptr<const unsigned char>(rk.iY), bf.ptr<const float>(rk.iP), ka, rk.st(bf));
-    for (int pass = 0; pass < rk.n_pass; ++pass) {
-        hipLaunchKernelGGL(k_radix_hist, dim3(rk.n_tiles), dim3(RK_NT), 0, bf.stm, rk.n, rk.n_tiles, pass, (const u64*)ka, (const u64*)kb,
-                           (const RankState*)rk.st(bf), bf.ptr<int>(rk.iCnt));
-        hipLaunchKernelGGL(k_radix_scan, dim3(1), dim3(1024), 0, bf.stm, rk.n, rk.n_tiles, pass, bf.ptr<int>(rk.iCnt), rk.st(bf));
-        hipLaunchKernelGGL(k_radix_scatter, dim3(rk.n_tiles), dim3(RK_NT), 0, bf.stm, rk.n, rk.n_tiles, pass, ka, kb, (const RankState*)rk.st(bf),
-                           bf.ptr<const int>(rk.iCnt));
-    }
+    radix_sort(bf.stm, ka, kb, rk.n, &rk.st(bf)->n, 0, rk.n_pass, bf.ptr<int>(rk.iCnt), &rk.st(bf)->rs);
     hipLaunchKernelGGL(k_rank_tile_sums, dim3(rk.n_tiles), dim3(RK_NT), 0, bf.stm, rk.n, (const u64*)ka, (const u64*)kb, rk.n_pass,
                        (const RankState*)rk.st(bf), bf.ptr<int>(rk.iTy), bf.ptr<int>(rk.iTg));
     hipLaunchKernelGGL(k_rank_tile_scan, dim3(1), dim3(1024), 0, bf.stm, rk.n_tiles, bf.ptr<int>(rk.iTy), bf.ptr<int>(rk.iTg),

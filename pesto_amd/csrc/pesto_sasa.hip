@@ -38,7 +38,7 @@
 #include <vector>
 
 #include "pesto_call.h"
-#include "pesto_cellgrid.h"      // struct_of and the one-workgroup scan; the grid here is its own (double, per frame, finite atoms only)
+#include "pesto_scan.h"
 
 namespace pesto {
 

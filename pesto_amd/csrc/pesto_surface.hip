@@ -15,14 +15,14 @@
 //                  nearest atom (atomicMax over the order-preserving map of the float's bits, -0.0 taken as +0.0); one thread per residue:
 //                  the label iface_area > 5.0 && iface_area / area > 0.04 and the score back from its bits.
 //   scored list    the residues with a vertex and a valid prediction, compacted per structure in residue order on the list protocol of
-//                  pesto_cellgrid.h (count -> k_list_offsets -> emit).
+//                  pesto_scan.h (count -> k_list_offsets -> emit).
 // There is no floating-point atomic in this file: every sum is an integer sum, every output the same bits from call to call.
 //
 // The C entry points (include/pesto_hip.h) live here too, on the call plumbing of pesto_call.h.
 #include <cmath>
 
 #include "pesto_call.h"
-#include "pesto_cellgrid.h"
+#include "pesto_scan.h"
 
 namespace pesto {
 

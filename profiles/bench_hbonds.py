@@ -69,7 +69,7 @@ def host_timed(fn):
 
 def source_hash():
     h = hashlib.sha256()
-    for rel in ("pesto_amd/csrc/pesto_hbonds.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/csrc/pesto_cellgrid.h", "pesto_amd/hbonds.py",
+    for rel in ("pesto_amd/csrc/pesto_hbonds.hip", "pesto_amd/csrc/pesto_geom.h", "pesto_amd/csrc/pesto_scan.h", "pesto_amd/hbonds.py",
                 "profiles/bench_hbonds.py"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]

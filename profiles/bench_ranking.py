@@ -58,7 +58,7 @@ def timed(fns):
 
 def source_hash():
     h = hashlib.sha256()
-    for rel in ("pesto_amd/csrc/pesto_rank.hip", "pesto_amd/csrc/pesto_eval.hip", "pesto_amd/csrc/pesto_cellgrid.h", "pesto_amd/ranking.py",
+    for rel in ("pesto_amd/csrc/pesto_rank.hip", "pesto_amd/csrc/pesto_eval.hip", "pesto_amd/csrc/pesto_radix.h", "pesto_amd/csrc/pesto_scan.h", "pesto_amd/ranking.py",
                 "profiles/bench_ranking.py"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]

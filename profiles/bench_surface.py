@@ -73,7 +73,7 @@ def ms(t):
 
 def source_hash():
     h = hashlib.sha256()
-    for rel in ("pesto_amd/csrc/pesto_surface.hip", "pesto_amd/csrc/pesto_rank.hip", "pesto_amd/csrc/pesto_cellgrid.h", "pesto_amd/surface.py",
+    for rel in ("pesto_amd/csrc/pesto_surface.hip", "pesto_amd/csrc/pesto_rank.hip", "pesto_amd/csrc/pesto_scan.h", "pesto_amd/surface.py",
                 "profiles/bench_surface.py"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]

@@ -23,7 +23,7 @@ Edge sets (the constants are read from the sources named; tests assert the cover
     pesto_trajectory.hip  CT = 16 (count tile), CF = 32 frames staged, FU = 4 frames side by side, LT = 32, LF = 64, JU = 4, bins: B with
                           top < B and an empty bin
     pesto_hbonds.hip      HB_ROWS = 8, HB_TILE = 32 (= hbonds.DONOR_TILE), 64-lane acceptor walk, NT = 256 (k_frame_scan over P and over the
-                          acceptor blocks), LIST_SCAN_NT = 1024 (pesto_cellgrid.h: frames of frame_hbonds, donor pairs of the occupancy list)
+                          acceptor blocks), LIST_SCAN_NT = 1024 (pesto_scan.h: frames of frame_hbonds, donor pairs of the occupancy list)
     pesto_docking.hip     FC_ROWS = 8, FC_TILE = 32, 64-lane partner walk, NT = 256 (k_frame_scan over Na), SCAN_NT = 1024 (over F)
     pesto_sasa.hip        NT = 256, WAVES = 4 atoms per workgroup, TILE = 256 candidate records, MB = 64 points per mask
     pesto_fit.h           NT = 256 threads stride a selection (the superposition fit of the trajectory, docking and DockQ groups), 64-lane waves

@@ -6,8 +6,9 @@ vectorised NumPy definitions below, which the fixture test pins to the restateme
 / np_typed_keys and the recorded dataset_*.npz, the recorded eval_scores.npz, test_patches_fixture.definition). Inputs come from
 numpy.random.default_rng([seed, attempt]); no builder looks at the library.
 
-contacts (pesto_contacts.hip behind the cell grid: RS_TILE = 256 keys per radix tile, the 1024-thread k_ct_scan, k_ct_gather's search over
-the per-atom offsets, the typed keys whose 22-bit group field lies in key bits 42..63, the swapped keys' second sort, the capacities)
+contacts (pesto_contacts.hip behind the cell grid: the radix sort of pesto_radix.h, RADIX_TILE = 2048 keys per tile in 8 rounds of 256 and
+a result that lies in the second buffer after an odd number of moving passes; the 1024-thread k_ct_scan, k_ct_gather's search over the
+per-atom offsets, the typed keys whose 22-bit group field lies in key bits 42..63, the swapped keys' second sort, the capacities)
     family = lattice | rough, + typed | untyped | mix (about 30 % untyped) | planted (mix, and two planted residue pairs: typed contacts
     then an untyped LAST one - no key -, untyped contacts then a typed LAST one - a key), + nt128 | nt1 (n_types, else 79 = MOLECULE_IDS;
     nt128 has type 127 on both sides of a key), + r8191 (the first contact lies in residues 0, the last, typed, in residues 8191)
@@ -76,6 +77,10 @@ CONTACTS = (
     ("rough+mix", 319, (("ball", 5, 23), ("comb", 0, 1, 0, 0), ("fan", 70), ("cloud", 4, 90), ("ball", 3, 3), ("comb", 7, 2, 1, 1))),
     ("lattice+mix+r8191", 320, (("cloud", 6, 200), ("fan", 66))),
     ("rough+mix", 321, (("ball", 40, 23),)),
+    ("lattice+mix", 323, (("comb", 2047, 5, 0, 0),)),
+    ("rough+typed", 324, (("comb", 2048, 5, 0, 1),)),
+    ("lattice+planted", 325, (("comb", 2000, 4, 0, 0), ("comb", 49, 1, 1, 0))),
+    ("rough+mix", 326, (("comb", 4000, 5, 0, 0), ("comb", 97, 1, 1, 1))),
     ("lattice+mix+nt1", 322, (("ball", 260, 2),)),              # K = 134,680, G = 33,670: three calls at the default capacities
 )
 BIG_BALL = CONTACTS[-1]
@@ -203,8 +208,19 @@ def contacts_def(X, sub, res, typ, offs, n_types, r_thr=R_THR):
     rkeys = np.ascontiguousarray(keys[rev][:, [1, 0, 3, 2]])
     T = np.zeros((G, n_types, n_types), np.uint8)
     T[kg, t0[pick], t1[pick]] = 1
+    # what the three radix sorts order by, from their lowest sorted bit up: the subunit pair (32 bits), (group, r0, r1) of every contact
+    # and (group, r1, r0) of every typed key (48 bits each)
+    sort_keys = dict(regroup=gkey, typed=key, swapped=(kg << 26) | (r1[pick] << 13) | r0[pick])
     return dict(pairs=np.stack([a, b], 1).astype(np.int32).reshape(-1, 2), d=d, groups=groups, keys=keys, rkeys=rkeys, T=T, ties=ties, K=int(K), G=int(G),
-                U=int(pick.size), run_key=key, gid=gid)
+                U=int(pick.size), run_key=key, gid=gid, sort_keys=sort_keys)
+
+
+SORT_BYTES = dict(regroup=4, typed=6, swapped=6)
+
+
+def moving_passes(keys, n_bytes):
+    """radix passes of 8 bits that move keys: every pass but those in which all keys share the digit (none of no key)"""
+    return sum(1 for i in range(n_bytes) if np.unique((keys >> (8 * i)) & 255).size > 1)
 
 
 def n_types_of(flags):
@@ -556,10 +572,11 @@ def coverage():
 
     def hit(entry, name, values):
         t.setdefault((entry, name), set()).update(values)
-    for family, _, shape in CONTACTS:
+    for case in CONTACTS:
+        family, _, shape = case
         kind, flags = parse(family)
         _, n_sub, K, G = _call_sizes(shape)
-        hit("contacts", "RS_TILE,scan:K", [K]); hit("contacts", "G", [G]); hit("contacts", "G>16384", [G is not None and G > 16384])
+        hit("contacts", "RADIX_TILE,rounds,scan:K", [K]); hit("contacts", "G", [G]); hit("contacts", "G>16384", [G is not None and G > 16384])
         hit("contacts", "n_sub", [n_sub]); hit("contacts", "assemblies", [len(shape)]); hit("contacts", "coordinates", [kind])
         hit("contacts", "types", flags & {"typed", "untyped", "mix", "planted"}); hit("contacts", "n_types", [n_types_of(flags)])
         hit("contacts", "residues 0 and 8191", ["r8191" in flags])
@@ -569,6 +586,11 @@ def coverage():
         hit("contacts", "features", ["lone subunit"] if any(s[0] == "comb" and s[4] for s in specs) else [])
         hit("contacts", "features", ["single-atom subunits"] if any(s[0] == "comb" and s[3] for s in specs) else [])
         hit("contacts", "features", ["descending partners >= 64"] if any(s[0] == "fan" and s[1] >= 64 for s in specs) else [])
+        # per sort the number of passes that move keys, from the case's own definition keys, and its class: an odd number leaves the
+        # sorted keys in the second buffer
+        for name, keys in build("contacts", case)["want"]["sort_keys"].items():
+            moves = moving_passes(keys, SORT_BYTES[name])
+            hit("contacts", f"{name} sort: moving passes", [moves, "0" if moves == 0 else "odd" if moves % 2 else "even > 0"])
     for family, _, (sizes, C) in SCORES:
         hit("scores", "BC_THREADS,BC_TILE:R", sizes); hit("scores", "C", [C]); hit("scores", "S", [len(sizes)]); hit("scores", "family", [family])
     for family, _, (structs, C) in PATCHES:
@@ -583,7 +605,9 @@ def coverage():
 
 
 REQUIRED = {
-    ("contacts", "RS_TILE,scan:K"): {0, 1, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025}, ("contacts", "G"): {0, 1, 63, 64, 65, 255, 256, 257},
+    ("contacts", "RADIX_TILE,rounds,scan:K"): {0, 1, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4097},
+    ("contacts", "regroup sort: moving passes"): {"0", "odd", "even > 0"}, ("contacts", "typed sort: moving passes"): {"0", "odd", "even > 0"},
+    ("contacts", "swapped sort: moving passes"): {"0", "odd", "even > 0"}, ("contacts", "G"): {0, 1, 63, 64, 65, 255, 256, 257},
     ("contacts", "G>16384"): {True}, ("contacts", "n_sub"): {2, 3, 255, 256, 257}, ("contacts", "assemblies"): {1, 2, 3, 6},
     ("contacts", "features"): {"K = 0 between", "lone subunit", "single-atom subunits", "descending partners >= 64"},
     ("contacts", "residues 0 and 8191"): {True}, ("contacts", "types"): {"typed", "untyped", "mix", "planted"}, ("contacts", "n_types"): {79, 128, 1},

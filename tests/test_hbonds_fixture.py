@@ -15,7 +15,7 @@ import pytest
 from conftest import GOLDEN, ROOT, golden
 
 DONOR_TILE = 32                         # PESTO_HBONDS_DONOR_TILE, the T of the `tiles` system
-SCAN_BLOCK = 1024                       # LIST_SCAN_NT of pesto_cellgrid.h, and more than the 256-thread frame scan
+SCAN_BLOCK = 1024                       # LIST_SCAN_NT of pesto_scan.h, and more than the 256-thread frame scan
 TILE_P = (1, DONOR_TILE - 1, DONOR_TILE, DONOR_TILE + 1)
 TILE_A = (1, 63, 64, 65, 129)
 FREQS = (0.0, 0.1, 0.5, 0.9)

@@ -12,7 +12,7 @@ import pytest
 
 from conftest import ROOT, golden
 
-TILE = 2048                             # pesto_rank.hip: RK_TILE, the keys one workgroup handles per radix pass (ranking.RADIX_TILE)
+TILE = 2048                             # pesto_radix.h: RADIX_TILE, the keys one workgroup handles per radix pass (ranking.RADIX_TILE)
 EVAL_CASES = ["pdbs53_logits", "pdbs53_bfactor", "synth"]          # inputs in eval_scores.npz
 POOLED = ["pdbs53_logits", "pdbs53_bfactor"]                       # recorded once more as one column of 16,825 rows (<case>_pool)
 NEW_CASES = ["edge", "cols255", "cols256", "cols257", "cols128", "cols129"]     # inputs in ranking.npz itself
@@ -238,5 +238,6 @@ def test_new_symbols_are_declared_exported_and_bound():
     import pesto_amd
     from pesto_amd import ranking
     assert ranking.RADIX_TILE == TILE and pesto_amd.roc_curve is ranking.roc_curve and pesto_amd.ranking is ranking
-    src = open(os.path.join(ROOT, "pesto_amd", "csrc", "pesto_rank.hip")).read()
-    assert "RK_TILE = PESTO_RANK_TILE" in src and "pesto_rank.hip" in open(os.path.join(ROOT, "pesto_amd", "csrc", "build.py")).read()
+    src = open(os.path.join(ROOT, "pesto_amd", "csrc", "pesto_radix.h")).read()
+    build_py = open(os.path.join(ROOT, "pesto_amd", "csrc", "build.py")).read()
+    assert "RADIX_TILE = PESTO_RANK_TILE" in src and "pesto_rank.hip" in build_py and "pesto_radix.h" in build_py
