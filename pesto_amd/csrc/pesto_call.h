@@ -1,5 +1,12 @@
-// pesto_call.h - the host plumbing of one analysis call (pesto_eval / patches / contacts / trajectory / sasa / dssp / rank / surface .hip): the group's message
-// channel, the handle's synchronisation, the offsets check and the call's one stream-ordered allocation with its staged copies.
+// pesto_call.h - the host plumbing of one analysis call (pesto_eval / patches / contacts / trajectory / sasa / dssp / rank / surface /
+// docking / dockq / hbonds / lddt / cluster / peaks / dynamics .hip, and the message channel of pesto_train.hip): the group's message
+// channel, the handle's synchronisation, the offsets check, the launch shape and the call's one stream-ordered allocation with its staged
+// copies, its cleared buffers and the read of the device's verdict.
+//
+// The protocol of one call: declare the buffers (a cleared one with its fill byte) -> upload() -> launch -> verdict(), where the host
+// needs the device's verdict before it goes on (to size a list: list_tail of pesto_scan.h; to refuse before anything is written;
+// between two phases), or read() of it where it is decoded only after finish() -> finish() -> decode the error bits into the group's
+// own messages.
 //
 // Everything sits in an anonymous namespace, so every translation unit that includes this header keeps a message of its own
 // (pesto_*_last_error of that group returns last_error()). These entry points need only the handle's device (pesto_synchronize sets it and
@@ -66,30 +73,35 @@ int check_offsets(const int32_t* offs, int32_t n, int64_t total, const char* wha
     return s < 0 ? 0 : fail(PESTO_ERR_INVALID, "%s: empty or unordered %s %d", what, unit, s);
 }
 
+// workgroups of nt threads over n items
+unsigned blocks(size_t n, int nt) { return (unsigned)((n + nt - 1) / nt); }
+
 // The buffers of one call, declared first and then allocated as ONE stream-ordered block that finish() frees on every path. Inputs and
 // outputs are the caller's own pointers on the device side and staged copies on the host side (a NULL one stays NULL on either side);
-// scratch and host-made tables always live in the block. upload() allocates and copies the staged inputs and the tables in; finish()
-// checks the launches, copies the staged outputs out, frees and synchronises.
+// scratch and host-made tables always live in the block. upload() allocates, copies the staged inputs and the tables in and clears the
+// outputs and scratch declared with a fill byte (the caller's own arrays too, on the device side); finish() checks the launches, copies
+// the staged outputs out, frees and synchronises.
 struct Buffers {
-    struct Item { const void* in; void* out; size_t bytes, at; bool own, whole; };
+    struct Item { const void* in; void* out; size_t bytes, at; bool own, whole; int fill; };
     bool dev;
     hipStream_t stm;
     char* w = nullptr;
     size_t total = 0;
     std::vector<Item> items;
     Buffers(int32_t ptr_kind, void* stream) : dev(ptr_kind == PESTO_PTR_DEVICE), stm((hipStream_t)stream) {}
-    int add(const void* in, void* out, size_t bytes, bool own, bool whole = true) {
-        Item it{in, out, bytes, total, own, whole};
+    int add(const void* in, void* out, size_t bytes, bool own, bool whole = true, int fill = -1) {
+        Item it{in, out, bytes, total, own, whole, fill};
         if (own) total += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
         items.push_back(it);
         return (int)items.size() - 1;
     }
     int input(const void* p, size_t bytes) { return add(p, nullptr, bytes, !dev && p); }
     int table(const void* host, size_t bytes) { return add(host, nullptr, bytes, true); }
-    int output(void* p, size_t bytes) { return add(nullptr, p, bytes, !dev && p); }
+    // (fill >= 0, here and for scratch: every byte is set to it before the call's first launch)
+    int output(void* p, size_t bytes, int fill = -1) { return add(nullptr, p, bytes, !dev && p, true, fill); }
     // an output of which the call itself brings back what it filled (fetch); finish() leaves it alone
-    int partial(void* p, size_t bytes) { return add(nullptr, p, bytes, !dev && p, false); }
-    int scratch(size_t bytes) { return add(nullptr, nullptr, bytes, true); }
+    int partial(void* p, size_t bytes, int fill = -1) { return add(nullptr, p, bytes, !dev && p, false, fill); }
+    int scratch(size_t bytes, int fill = -1) { return add(nullptr, nullptr, bytes, true, true, fill); }
     template <class T> T* ptr(int i) const {
         const Item& it = items[i];
         if (it.own) return (T*)(w + it.at);
@@ -103,7 +115,15 @@ struct Buffers {
         for (const Item& it : items)
             if (it.own && it.in)
                 if (int rc = hip_ok(hipMemcpyAsync(w + it.at, it.in, it.bytes, hipMemcpyHostToDevice, stm), "copy to the device failed")) return rc;
+        for (int i = 0; i < (int)items.size(); ++i)
+            if (items[i].fill >= 0 && items[i].bytes && ptr<void>(i))
+                if (int rc = hip_ok(hipMemsetAsync(ptr<void>(i), items[i].fill, items[i].bytes, stm), "clearing a device buffer failed")) return rc;
         return 0;
+    }
+    // 0, or PESTO_ERR_HIP with "<what>: launch failed: <HIP's message>"
+    int launched(const char* what) {
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : fail(PESTO_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     }
     // the first `bytes` of item i to host memory, in stream order
     int read(int i, void* host, size_t bytes) {
@@ -111,11 +131,16 @@ struct Buffers {
     }
     // the first `bytes` of a staged output to the caller's array (nothing to do on the device side)
     int fetch(int i, size_t bytes) { return items[i].own && items[i].out && bytes ? read(i, items[i].out, bytes) : 0; }
+    // the device's verdict on what has been launched so far: the launch check, the first `bytes` of item i to `host` and the call's one
+    // synchronisation before finish()
+    int verdict(int i, void* host, size_t bytes, const char* what) {
+        if (int rc = launched(what)) return rc;
+        if (int rc = read(i, host, bytes)) return rc;
+        const hipError_t e = hipStreamSynchronize(stm);
+        return e == hipSuccess ? 0 : fail(PESTO_ERR_HIP, "%s: stream synchronisation failed: %s", what, hipGetErrorString(e));
+    }
     int finish(int rc, const char* what) {
-        if (rc == 0) {
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) rc = fail(PESTO_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-        }
+        if (rc == 0) rc = launched(what);
         if (rc == 0)
             for (const Item& it : items)
                 if (it.own && it.out && it.whole) {

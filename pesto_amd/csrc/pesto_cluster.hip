@@ -294,7 +294,7 @@ int pesto_gromos_clusters(pesto_model* m, int64_t F, const float* D, float cutof
                 hipLaunchKernelGGL(k_cl_pick, dim3(1), dim3(1024), 0, bf.stm, (int)F, W, adj, cnt, act, mem, bf.ptr<int>(iL), bf.ptr<int>(iC), bf.ptr<int>(iZ), st);
                 hipLaunchKernelGGL(k_cl_update, dim3((unsigned)((F + NT / 64 - 1) / (NT / 64))), dim3(NT), 0, bf.stm, (int)F, W, adj, act, mem, cnt, st);
             }
-            if ((rc = bf.read(iSt, state, sizeof state)) == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "gromos_clusters");
+            rc = bf.verdict(iSt, state, sizeof state, "gromos_clusters");
             // the matrix is an argument: its symmetry is known with the first read of the state, the call's one argument check on the device
             if (rc == 0 && state[ST_ASYM]) rc = fail(PESTO_ERR_INVALID, "D is not bitwise symmetric");
         }

@@ -231,8 +231,6 @@ void launch_contacts(hipStream_t s, int n_total, int n_struct, int n_sub, const 
                      int n_types, float r_thr, int cap_pairs, int cap_groups, const CtBuffers& w, int* pairs_out, float* d_out, int* groups_out,
                      unsigned short* keys_out, unsigned short* rkeys_out, unsigned char* T_out, unsigned char* ties_out) {
     const int nb = (n_total + 255) / 256, nbk = (cap_pairs + 255) / 256;
-    (void)hipMemsetAsync(groups_out, 0, (size_t)cap_groups * 16, s);
-    (void)hipMemsetAsync(T_out, 0, (size_t)cap_groups * n_types * n_types, s);
     hipLaunchKernelGGL(k_grid_setup, dim3(n_struct), dim3(256), 0, s, n_struct, (const int*)w.offsets, X, r_thr, w.grids, w.cell_cnt);
     hipLaunchKernelGGL(k_grid_count<CtCheck>, dim3(nb), dim3(256), 0, s, n_total, n_struct, (const int*)w.offsets, X, (const CellGrid*)w.grids,
                        w.cell_cnt, w.cell_of, CtCheck{w.offsets, subunit, residue, type, n_sub, n_types, w.st});
@@ -299,16 +297,15 @@ int pesto_contacts(pesto_model* m, int64_t n_total, int32_t n_struct, const int3
     Buffers bf(ptr_kind, stream);
     const int iOff = bf.table(struct_offsets, ((size_t)n_struct + 1) * 4), iX = bf.input(X, n * 12), iS = bf.input(subunit, n * 4),
               iR = bf.input(residue, n * 4), iT = bf.input(type, n * 4);
-    // the outputs come back as far as the counters say they were filled; ties whole
-    const int iP = bf.partial(pairs_out, C * 8), iD = bf.partial(d_out, C * 4), iGr = bf.partial(groups_out, Cg * 16), iK = bf.partial(keys_out, C * 8),
-              iRk = bf.partial(rkeys_out, C * 8), iTt = bf.partial(T_out, Cg * nt2), iTi = bf.output(ties_out, n);
-    const int iSt = bf.scratch(sizeof(CtState)), iG = bf.scratch((size_t)n_struct * sizeof(CellGrid)), iCnt = bf.scratch(cells * 4),
+    // the outputs come back as far as the counters say they were filled; ties whole. The groups and their type matrices start at zero.
+    const int iP = bf.partial(pairs_out, C * 8), iD = bf.partial(d_out, C * 4), iGr = bf.partial(groups_out, Cg * 16, 0), iK = bf.partial(keys_out, C * 8),
+              iRk = bf.partial(rkeys_out, C * 8), iTt = bf.partial(T_out, Cg * nt2, 0), iTi = bf.output(ties_out, n);
+    const int iSt = bf.scratch(sizeof(CtState), 0), iG = bf.scratch((size_t)n_struct * sizeof(CellGrid)), iCnt = bf.scratch(cells * 4),
               iCur = bf.scratch(cells * 4), iCell = bf.scratch(n * 4), iSort = bf.scratch(n * 16), iSub = bf.scratch(n * 4),
               iAOff = bf.scratch((n + 1) * 4), iPb = bf.scratch(C * 4), iPd = bf.scratch(C * 4), iGk = bf.scratch(C * 8), iTk = bf.scratch(C * 8),
               iRk8 = bf.scratch(C * 8), iTmp = bf.scratch(C * 8), iFlag = bf.scratch(C * 4), iHist = bf.scratch(radix_counter_bytes(C));
     CtState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<CtState>(iSt), 0, sizeof(CtState), bf.stm), "contacts");
     if (rc == 0) {
         const CtBuffers b{bf.ptr<int>(iOff), bf.ptr<CtState>(iSt), bf.ptr<CellGrid>(iG), bf.ptr<int>(iCnt), bf.ptr<int>(iCur), bf.ptr<int>(iCell),
                           bf.ptr<float4>(iSort), bf.ptr<int>(iSub), bf.ptr<int>(iAOff), bf.ptr<int>(iPb), bf.ptr<float>(iPd), bf.ptr<u64>(iGk),
@@ -316,11 +313,9 @@ int pesto_contacts(pesto_model* m, int64_t n_total, int32_t n_struct, const int3
         launch_contacts(bf.stm, (int)n_total, n_struct, n_sub, bf.ptr<const float>(iX), bf.ptr<const int>(iS), bf.ptr<const int>(iR),
                         bf.ptr<const int>(iT), n_types, r_thr, (int)C, (int)Cg, b, bf.ptr<int>(iP), bf.ptr<float>(iD), bf.ptr<int>(iGr),
                         bf.ptr<unsigned short>(iK), bf.ptr<unsigned short>(iRk), bf.ptr<unsigned char>(iTt), bf.ptr<unsigned char>(iTi));
-        rc = hip_ok(hipGetLastError(), "contacts: launch failed");
     }
     // the one synchronisation for sizing: the counters
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(CtState));
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "contacts: stream synchronisation failed");
+    if (rc == 0) rc = bf.verdict(iSt, &hs, sizeof hs, "contacts");
     if (rc == 0) {
         const bool fits = hs.n_sort == hs.K;
         sizes_out[0] = hs.K;

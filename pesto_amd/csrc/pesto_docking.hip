@@ -25,10 +25,8 @@ namespace {
 constexpr int NT = 256;                 // threads per workgroup of every kernel here
 constexpr int FC_ROWS = 8;              // frame contacts: atoms of A per wave (their partners' coordinates are loaded once for all of them)
 constexpr int FC_TILE = FC_ROWS * NT / 64;      // ... and per workgroup
-constexpr int SCAN_NT = LIST_SCAN_NT;   // threads of the one workgroup that scans the frames' totals (k_list_offsets, pesto_scan.h)
 
-// the device counters of one call (pesto_scan.h); err bit 0: an atom index outside its side; bit 1: a residue row outside 0 .. R - 1
-using DkState = ListState;
+// err of the call's ListState (pesto_scan.h): bit 0: an atom index outside its side; bit 1: a residue row outside 0 .. R - 1
 
 // ------------------------------------------------------------------------------------------------ frame contacts
 // replaces: the frame loop of contacts (md_analysis/mdtraj_utils/trajectory_utils.py:408-423; a dense [Na, Nb] matrix, torch.where and
@@ -39,7 +37,7 @@ using DkState = ListState;
 template <bool EMIT>
 __global__ __launch_bounds__(NT) void k_fc_pairs(int Na, int Nb, int tiles, const float* __restrict__ xa, const float* __restrict__ xb, float s_star,
                                                  float scale, int* __restrict__ cnt, const long long* __restrict__ foff,
-                                                 const DkState* __restrict__ st, int* __restrict__ pairs, float* __restrict__ d) {
+                                                 const ListState* __restrict__ st, int* __restrict__ pairs, float* __restrict__ d) {
     if (EMIT && !st->fits) return;
     const size_t f = blockIdx.x / (unsigned)tiles;
     const int lane = threadIdx.x & 63;
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(NT) void k_fc_pairs(int Na, int Nb, int tiles, cons
 // the word and bit of contact k, false (and an error bit) for an index outside its range
 __device__ __forceinline__ bool contact_bit(long long k, int F, int Na, int Nb, int Ra, int Rb, int W, const long long* __restrict__ off,
                                             const int* __restrict__ pairs, const int* __restrict__ res_a, const int* __restrict__ res_b,
-                                            DkState* __restrict__ st, size_t& word, int& bit) {
+                                            ListState* __restrict__ st, size_t& word, int& bit) {
     const int i = pairs[2 * k], j = pairs[2 * k + 1];
     if (i < 0 || i >= Na || j < 0 || j >= Nb) { atomicOr(&st->err, 1); return false; }
     const int ra = res_a[i], rb = res_b[j];
@@ -107,7 +105,7 @@ __device__ __forceinline__ bool contact_bit(long long k, int F, int Na, int Nb, 
 
 __global__ __launch_bounds__(NT) void k_rc_mark(long long K, int F, int Na, int Nb, int Ra, int Rb, int W, const long long* __restrict__ off,
                                                 const int* __restrict__ pairs, const int* __restrict__ res_a, const int* __restrict__ res_b,
-                                                DkState* __restrict__ st, unsigned* __restrict__ bits) {
+                                                ListState* __restrict__ st, unsigned* __restrict__ bits) {
     const long long k = (long long)blockIdx.x * NT + threadIdx.x;
     if (k >= K) return;
     size_t word;
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(NT) void k_rc_count(size_t n_words, const unsigned*
 
 // the residue pairs of every word's set bits, their minimum at +inf
 __global__ __launch_bounds__(NT) void k_rc_emit(size_t n_words, int W, int Rb, const unsigned* __restrict__ bits, const int* __restrict__ woff,
-                                                const long long* __restrict__ roff, const DkState* __restrict__ st, int* __restrict__ rpairs,
+                                                const long long* __restrict__ roff, const ListState* __restrict__ st, int* __restrict__ rpairs,
                                                 unsigned* __restrict__ dmin_bits) {
     if (!st->fits) return;
     const size_t w = (size_t)blockIdx.x * NT + threadIdx.x;
@@ -142,7 +140,7 @@ __global__ __launch_bounds__(NT) void k_rc_emit(size_t n_words, int W, int Rb, c
 
 __global__ __launch_bounds__(NT) void k_rc_min(long long K, int F, int Na, int Nb, int Ra, int Rb, int W, const long long* __restrict__ off,
                                                const int* __restrict__ pairs, const float* __restrict__ d, const int* __restrict__ res_a,
-                                               const int* __restrict__ res_b, DkState* __restrict__ st, const unsigned* __restrict__ bits,
+                                               const int* __restrict__ res_b, ListState* __restrict__ st, const unsigned* __restrict__ bits,
                                                const int* __restrict__ woff, const long long* __restrict__ roff, unsigned* __restrict__ dmin_bits) {
     if (!st->fits) return;
     const long long k = (long long)blockIdx.x * NT + threadIdx.x;
@@ -160,7 +158,7 @@ __global__ __launch_bounds__(NT) void k_rc_min(long long K, int F, int Na, int N
 // idempotent store), and every atom of the topology takes the flag of its residue. rflag: [2][R], zeroed.
 __global__ __launch_bounds__(NT) void k_ia_hits(int N, int na, int nb, int R, const float* __restrict__ x, const int* __restrict__ ids_a,
                                                 const int* __restrict__ ids_b, const int* __restrict__ res, float s_star, int* __restrict__ rflag,
-                                                DkState* __restrict__ st) {
+                                                ListState* __restrict__ st) {
     const int t = blockIdx.x * NT + threadIdx.x;
     if (t >= na + nb) return;
     const bool side_b = t >= na;
@@ -182,7 +180,7 @@ __global__ __launch_bounds__(NT) void k_ia_hits(int N, int na, int nb, int R, co
     }
 }
 
-__global__ __launch_bounds__(NT) void k_ia_flags(int N, int R, const int* __restrict__ res, const int* __restrict__ rflag, DkState* __restrict__ st,
+__global__ __launch_bounds__(NT) void k_ia_flags(int N, int R, const int* __restrict__ res, const int* __restrict__ rflag, ListState* __restrict__ st,
                                                  unsigned char* __restrict__ flags) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= N) return;
@@ -261,8 +259,6 @@ int check_cutoff(float r_thr, float scale) {
     return 0;
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
-
 }  // namespace
 }  // namespace pesto
 
@@ -286,32 +282,21 @@ int pesto_frame_contacts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
     Buffers bf(ptr_kind, stream);
     const int iA = bf.input(xyz_a, (size_t)F * Na * 12), iB = bf.input(xyz_b, (size_t)F * Nb * 12);
     const int iO = bf.output(offsets_out, ((size_t)F + 1) * 8), iP = bf.partial(pairs_out, C * 8), iD = bf.partial(d_out, C * 4);
-    const int iSt = bf.scratch(sizeof(DkState)), iCnt = bf.scratch((size_t)F * Na * 4), iTot = bf.scratch((size_t)F * 4);
-    DkState hs = {};
+    const int iSt = bf.scratch(sizeof(ListState), 0), iCnt = bf.scratch((size_t)F * Na * 4), iTot = bf.scratch((size_t)F * 4);
+    ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<DkState>(iSt), 0, sizeof(DkState), bf.stm), "frame_contacts");
     if (rc == 0) {
         const dim3 grid((unsigned)(F * tiles));
         hipLaunchKernelGGL(k_fc_pairs<false>, grid, dim3(NT), 0, bf.stm, (int)Na, (int)Nb, (int)tiles, bf.ptr<const float>(iA), bf.ptr<const float>(iB),
-                           s_star, scale, bf.ptr<int>(iCnt), (const long long*)nullptr, (const DkState*)nullptr, (int*)nullptr, (float*)nullptr);
-        hipLaunchKernelGGL(k_frame_scan<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)Na, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
-        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(SCAN_NT), 0, bf.stm, (int)F, bf.ptr<const int>(iTot), bf.ptr<long long>(iO),
-                           (long long)cap_pairs, bf.ptr<DkState>(iSt));
+                           s_star, scale, bf.ptr<int>(iCnt), (const long long*)nullptr, (const ListState*)nullptr, (int*)nullptr, (float*)nullptr);
+        list_scan<NT>(bf, (int)F, (int)Na, iCnt, iTot, iO, (long long)cap_pairs, iSt);
         hipLaunchKernelGGL(k_fc_pairs<true>, grid, dim3(NT), 0, bf.stm, (int)Na, (int)Nb, (int)tiles, bf.ptr<const float>(iA), bf.ptr<const float>(iB),
-                           s_star, scale, bf.ptr<int>(iCnt), bf.ptr<const long long>(iO), bf.ptr<const DkState>(iSt), bf.ptr<int>(iP),
+                           s_star, scale, bf.ptr<int>(iCnt), bf.ptr<const long long>(iO), bf.ptr<const ListState>(iSt), bf.ptr<int>(iP),
                            bf.ptr<float>(iD));
-        rc = hip_ok(hipGetLastError(), "frame_contacts: launch failed");
     }
     // the one synchronisation for sizing: the count
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(DkState));
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "frame_contacts: stream synchronisation failed");
-    if (rc == 0) {
-        sizes_out[0] = hs.K;
-        if (hs.fits) {
-            rc = bf.fetch(iP, (size_t)hs.K * 8);
-            if (rc == 0) rc = bf.fetch(iD, (size_t)hs.K * 4);
-        }
-    }
+    if (rc == 0) rc = bf.verdict(iSt, &hs, sizeof hs, "frame_contacts");
+    if (rc == 0) rc = list_tail(bf, hs, sizes_out, {{iP, 8}, {iD, 4}});
     return bf.finish(rc, "frame_contacts");
 }
 
@@ -334,40 +319,28 @@ int pesto_frame_residue_contacts(pesto_model* m, int64_t F, int64_t Na, int64_t 
     const int iOff = bf.input(offsets, ((size_t)F + 1) * 8), iP = bf.input(pairs, Kz * 8), iD = bf.input(d, Kz * 4), iRa = bf.input(res_a, (size_t)Na * 4),
               iRb = bf.input(res_b, (size_t)Nb * 4);
     const int iO = bf.output(roffsets_out, ((size_t)F + 1) * 8), iRp = bf.partial(rpairs_out, C * 8), iDm = bf.partial(dmin_out, C * 4);
-    const int iSt = bf.scratch(sizeof(DkState)), iBits = bf.scratch(n_words * 4), iCnt = bf.scratch(n_words * 4), iTot = bf.scratch((size_t)F * 4);
-    DkState hs = {};
+    const int iSt = bf.scratch(sizeof(ListState), 0), iBits = bf.scratch(n_words * 4, 0), iCnt = bf.scratch(n_words * 4), iTot = bf.scratch((size_t)F * 4);
+    ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<DkState>(iSt), 0, sizeof(DkState), bf.stm), "frame_residue_contacts");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<unsigned>(iBits), 0, n_words * 4, bf.stm), "frame_residue_contacts");
     if (rc == 0) {
         const long long* off = bf.ptr<const long long>(iOff);
         const int *pr = bf.ptr<const int>(iP), *ra = bf.ptr<const int>(iRa), *rb = bf.ptr<const int>(iRb);
-        DkState* st = bf.ptr<DkState>(iSt);
+        ListState* st = bf.ptr<ListState>(iSt);
         if (K > 0)
-            hipLaunchKernelGGL(k_rc_mark, dim3(blocks(Kz)), dim3(NT), 0, bf.stm, (long long)K, (int)F, (int)Na, (int)Nb, Ra, Rb, (int)W, off, pr, ra, rb, st,
+            hipLaunchKernelGGL(k_rc_mark, dim3(blocks(Kz, NT)), dim3(NT), 0, bf.stm, (long long)K, (int)F, (int)Na, (int)Nb, Ra, Rb, (int)W, off, pr, ra, rb, st,
                                bf.ptr<unsigned>(iBits));
-        hipLaunchKernelGGL(k_rc_count, dim3(blocks(n_words)), dim3(NT), 0, bf.stm, n_words, bf.ptr<const unsigned>(iBits), bf.ptr<int>(iCnt));
-        hipLaunchKernelGGL(k_frame_scan<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)W, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
-        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(SCAN_NT), 0, bf.stm, (int)F, bf.ptr<const int>(iTot), bf.ptr<long long>(iO),
-                           (long long)cap_rpairs, st);
-        hipLaunchKernelGGL(k_rc_emit, dim3(blocks(n_words)), dim3(NT), 0, bf.stm, n_words, (int)W, Rb, bf.ptr<const unsigned>(iBits),
-                           bf.ptr<const int>(iCnt), bf.ptr<const long long>(iO), (const DkState*)st, bf.ptr<int>(iRp), bf.ptr<unsigned>(iDm));
+        hipLaunchKernelGGL(k_rc_count, dim3(blocks(n_words, NT)), dim3(NT), 0, bf.stm, n_words, bf.ptr<const unsigned>(iBits), bf.ptr<int>(iCnt));
+        list_scan<NT>(bf, (int)F, (int)W, iCnt, iTot, iO, (long long)cap_rpairs, iSt);
+        hipLaunchKernelGGL(k_rc_emit, dim3(blocks(n_words, NT)), dim3(NT), 0, bf.stm, n_words, (int)W, Rb, bf.ptr<const unsigned>(iBits),
+                           bf.ptr<const int>(iCnt), bf.ptr<const long long>(iO), (const ListState*)st, bf.ptr<int>(iRp), bf.ptr<unsigned>(iDm));
         if (K > 0)
-            hipLaunchKernelGGL(k_rc_min, dim3(blocks(Kz)), dim3(NT), 0, bf.stm, (long long)K, (int)F, (int)Na, (int)Nb, Ra, Rb, (int)W, off, pr,
+            hipLaunchKernelGGL(k_rc_min, dim3(blocks(Kz, NT)), dim3(NT), 0, bf.stm, (long long)K, (int)F, (int)Na, (int)Nb, Ra, Rb, (int)W, off, pr,
                                bf.ptr<const float>(iD), ra, rb, st, bf.ptr<const unsigned>(iBits), bf.ptr<const int>(iCnt), bf.ptr<const long long>(iO),
                                bf.ptr<unsigned>(iDm));
-        rc = hip_ok(hipGetLastError(), "frame_residue_contacts: launch failed");
     }
     // the one synchronisation for sizing: the count
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(DkState));
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "frame_residue_contacts: stream synchronisation failed");
-    if (rc == 0) {
-        sizes_out[0] = hs.K;
-        if (hs.fits && !hs.err) {
-            rc = bf.fetch(iRp, (size_t)hs.K * 8);
-            if (rc == 0) rc = bf.fetch(iDm, (size_t)hs.K * 4);
-        }
-    }
+    if (rc == 0) rc = bf.verdict(iSt, &hs, sizeof hs, "frame_residue_contacts");
+    if (rc == 0) rc = list_tail(bf, hs, sizes_out, {{iRp, 8}, {iDm, 4}}, !hs.err);
     rc = bf.finish(rc, "frame_residue_contacts");
     if (rc == 0 && (hs.err & 1)) rc = fail(PESTO_ERR_INVALID, "pairs: atom indices must lie in [0, Na) and [0, Nb)");
     if (rc == 0 && (hs.err & 2)) rc = fail(PESTO_ERR_INVALID, "res_a / res_b: residue rows must lie in [0, Ra) and [0, Rb)");
@@ -385,19 +358,17 @@ int pesto_interface_atoms(pesto_model* m, int64_t N, const float* xyz0, int64_t 
     Buffers bf(ptr_kind, stream);
     const int iX = bf.input(xyz0, (size_t)N * 12), iA = bf.input(ids_a, (size_t)na * 4), iB = bf.input(ids_b, (size_t)nb * 4),
               iR = bf.input(res_of_atom, (size_t)N * 4), iF = bf.output(flags_out, (size_t)N * 2);
-    const int iSt = bf.scratch(sizeof(DkState)), iRf = bf.scratch((size_t)R * 8);
-    DkState hs = {};
+    const int iSt = bf.scratch(sizeof(ListState), 0), iRf = bf.scratch((size_t)R * 8, 0);
+    ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<DkState>(iSt), 0, sizeof(DkState), bf.stm), "interface_atoms");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iRf), 0, (size_t)R * 8, bf.stm), "interface_atoms");
     if (rc == 0) {
-        hipLaunchKernelGGL(k_ia_hits, dim3(blocks((size_t)(na + nb))), dim3(NT), 0, bf.stm, (int)N, (int)na, (int)nb, R, bf.ptr<const float>(iX),
-                           bf.ptr<const int>(iA), bf.ptr<const int>(iB), bf.ptr<const int>(iR), s_star, bf.ptr<int>(iRf), bf.ptr<DkState>(iSt));
-        hipLaunchKernelGGL(k_ia_flags, dim3(blocks((size_t)N)), dim3(NT), 0, bf.stm, (int)N, R, bf.ptr<const int>(iR), bf.ptr<const int>(iRf),
-                           bf.ptr<DkState>(iSt), bf.ptr<unsigned char>(iF));
-        rc = hip_ok(hipGetLastError(), "interface_atoms: launch failed");
+        hipLaunchKernelGGL(k_ia_hits, dim3(blocks((size_t)(na + nb), NT)), dim3(NT), 0, bf.stm, (int)N, (int)na, (int)nb, R, bf.ptr<const float>(iX),
+                           bf.ptr<const int>(iA), bf.ptr<const int>(iB), bf.ptr<const int>(iR), s_star, bf.ptr<int>(iRf), bf.ptr<ListState>(iSt));
+        hipLaunchKernelGGL(k_ia_flags, dim3(blocks((size_t)N, NT)), dim3(NT), 0, bf.stm, (int)N, R, bf.ptr<const int>(iR), bf.ptr<const int>(iRf),
+                           bf.ptr<ListState>(iSt), bf.ptr<unsigned char>(iF));
     }
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(DkState));
+    // (decoded after finish(), whose synchronisation brings it)
+    if (rc == 0) rc = bf.read(iSt, &hs, sizeof hs);
     rc = bf.finish(rc, "interface_atoms");
     if (rc == 0 && (hs.err & 1)) rc = fail(PESTO_ERR_INVALID, "ids_a / ids_b: atom indices must lie in [0, N)");
     if (rc == 0 && (hs.err & 2)) rc = fail(PESTO_ERR_INVALID, "res_of_atom: residue rows must lie in [0, R)");
@@ -414,13 +385,12 @@ int launch_docking(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const fl
     Buffers bf(ptr_kind, stream);
     const int iY = bf.input(xyz_ref, (size_t)F_ref * N * 12), iX = bf.input(xyz, (size_t)F * N * 12), iSr = bf.input(sel_R, (size_t)n_R * 4),
               iSl = bf.input(sel_L, (size_t)n_L * 4), iT = bf.output(t_out, (size_t)F * 12), iRv = bf.output(r_out, (size_t)F * 12),
-              iRm = bf.output(rmsd_out, (size_t)F * 4), iSt = bf.scratch(sizeof(int));
+              iRm = bf.output(rmsd_out, (size_t)F * 4), iSt = bf.scratch(sizeof(int), 0);
     int herr = 0;
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSt), 0, sizeof(int), bf.stm), what);
     if (rc == 0) {
         const IndexLists idx = {{bf.ptr<const int>(iSr), bf.ptr<const int>(iSl)}, {n_R, n_L}};
-        hipLaunchKernelGGL(k_index_check<NT>, dim3(blocks((size_t)idx.total())), dim3(NT), 0, bf.stm, (int)N, idx, bf.ptr<int>(iSt));
+        hipLaunchKernelGGL(k_index_check<NT>, dim3(blocks((size_t)idx.total(), NT)), dim3(NT), 0, bf.stm, (int)N, idx, bf.ptr<int>(iSt));
         if (t_out)
             hipLaunchKernelGGL(k_rigid_docking, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_R, (int)n_L, bf.ptr<const float>(iY),
                                bf.ptr<const float>(iX), bf.ptr<const int>(iSr), bf.ptr<const int>(iSl), bf.ptr<const int>(iSt), bf.ptr<float>(iT),
@@ -428,9 +398,8 @@ int launch_docking(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const fl
         else
             hipLaunchKernelGGL(k_fit_rmsd<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_R, (int)n_R, bf.ptr<const float>(iY),
                                bf.ptr<const float>(iX), bf.ptr<const int>(iSr), bf.ptr<const int>(iSr), bf.ptr<const int>(iSt), scale, bf.ptr<float>(iRm));
-        rc = hip_ok(hipGetLastError(), what);
     }
-    if (rc == 0) rc = bf.read(iSt, &herr, sizeof(int));
+    if (rc == 0) rc = bf.read(iSt, &herr, sizeof herr);
     rc = bf.finish(rc, what);
     if (rc == 0 && herr) rc = fail(PESTO_ERR_INVALID, "%s: atom indices of a selection must lie in [0, N)", what);
     return rc;

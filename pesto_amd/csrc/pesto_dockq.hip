@@ -130,8 +130,6 @@ __global__ __launch_bounds__(NT) void k_dockq(int N, int P, int nI, int nR, int 
 // pesto_fit.h)
 
 // ---- host side
-unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
-
 // the error of a refused call from the check kernel's bits (0: none)
 int index_error(int err, const char* what) {
     if (err & 1) return fail(PESTO_ERR_INVALID, "%s: atom indices of a selection or of the permutation must lie in [0, N)", what);
@@ -168,23 +166,20 @@ int pesto_dockq(pesto_model* m, int64_t F, int64_t N, const float* xyz_ref, cons
               iSl = bf.input(sel_L, (size_t)n_L * 4);
     const int iFn = bf.output(fnat_out, (size_t)F * 4), iKp = bf.output(preserved_out, (size_t)F * 4), iIr = bf.output(irmsd_out, (size_t)F * 4),
               iLr = bf.output(lrmsd_out, (size_t)F * 4), iDq = bf.output(dockq_out, (size_t)F * 4), iCp = bf.output(capri_out, (size_t)F);
-    const int iSt = bf.scratch(sizeof(int));
+    const int iSt = bf.scratch(sizeof(int), 0);
     int herr = 0;
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSt), 0, sizeof(int), bf.stm), "dockq");
     if (rc == 0) {
         const IndexLists idx = {{bf.ptr<const int>(iSi), bf.ptr<const int>(iSr), bf.ptr<const int>(iSl), bf.ptr<const int>(iPm)}, {n_I, n_R, n_L, n_perm}};
-        hipLaunchKernelGGL(k_dq_check, dim3(blocks((size_t)(idx.total() + P))), dim3(NT), 0, bf.stm, (int)N, idx, (long long)n_perm, (long long)P,
+        hipLaunchKernelGGL(k_dq_check, dim3(blocks((size_t)(idx.total() + P), NT)), dim3(NT), 0, bf.stm, (int)N, idx, (long long)n_perm, (long long)P,
                            bf.ptr<const int>(iPr), bf.ptr<int>(iSt));
         hipLaunchKernelGGL(k_dockq, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)N, (int)P, (int)n_I, (int)n_R, (int)n_L, bf.ptr<const float>(iY),
                            bf.ptr<const float>(iX), bf.ptr<const int>(iPm), bf.ptr<const int>(iPr), bf.ptr<const int>(iSi), bf.ptr<const int>(iSr),
                            bf.ptr<const int>(iSl), bf.ptr<const int>(iSt), s_star, scale, bf.ptr<float>(iFn), bf.ptr<int>(iKp), bf.ptr<float>(iIr),
                            bf.ptr<float>(iLr), bf.ptr<float>(iDq), bf.ptr<unsigned char>(iCp));
-        rc = hip_ok(hipGetLastError(), "dockq: launch failed");
     }
     // a refused call writes nothing: the check's verdict is read before any output is copied back
-    if (rc == 0) rc = bf.read(iSt, &herr, sizeof(int));
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "dockq: stream synchronisation failed");
+    if (rc == 0) rc = bf.verdict(iSt, &herr, sizeof herr, "dockq");
     if (rc == 0) rc = index_error(herr, "dockq");
     return bf.finish(rc, "dockq");
 }
@@ -198,19 +193,16 @@ int pesto_fit_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const fl
     if (int rc = begin(m, ptr_kind)) return rc;
     Buffers bf(ptr_kind, stream);
     const int iY = bf.input(xyz_ref, (size_t)F_ref * N * 12), iX = bf.input(xyz, (size_t)F * N * 12), iSf = bf.input(sel_fit, (size_t)n_fit * 4),
-              iSm = bf.input(sel_measure, (size_t)n_measure * 4), iO = bf.output(rmsd_out, (size_t)F * 4), iSt = bf.scratch(sizeof(int));
+              iSm = bf.input(sel_measure, (size_t)n_measure * 4), iO = bf.output(rmsd_out, (size_t)F * 4), iSt = bf.scratch(sizeof(int), 0);
     int herr = 0;
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSt), 0, sizeof(int), bf.stm), "fit_rmsd");
     if (rc == 0) {
         const IndexLists idx = {{bf.ptr<const int>(iSf), bf.ptr<const int>(iSm)}, {n_fit, n_measure}};
-        hipLaunchKernelGGL(k_index_check<NT>, dim3(blocks((size_t)idx.total())), dim3(NT), 0, bf.stm, (int)N, idx, bf.ptr<int>(iSt));
+        hipLaunchKernelGGL(k_index_check<NT>, dim3(blocks((size_t)idx.total(), NT)), dim3(NT), 0, bf.stm, (int)N, idx, bf.ptr<int>(iSt));
         hipLaunchKernelGGL(k_fit_rmsd<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)F_ref, (int)N, (int)n_fit, (int)n_measure, bf.ptr<const float>(iY),
                            bf.ptr<const float>(iX), bf.ptr<const int>(iSf), bf.ptr<const int>(iSm), bf.ptr<const int>(iSt), scale, bf.ptr<float>(iO));
-        rc = hip_ok(hipGetLastError(), "fit_rmsd: launch failed");
     }
-    if (rc == 0) rc = bf.read(iSt, &herr, sizeof(int));
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "fit_rmsd: stream synchronisation failed");
+    if (rc == 0) rc = bf.verdict(iSt, &herr, sizeof herr, "fit_rmsd");
     if (rc == 0) rc = index_error(herr, "fit_rmsd");
     return bf.finish(rc, "fit_rmsd");
 }

@@ -384,8 +384,6 @@ __global__ __launch_bounds__(NT) void k_dssp_tail(int R_total, int n_struct, con
     }
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
-
 }  // namespace
 }  // namespace pesto
 
@@ -435,7 +433,7 @@ int pesto_dssp(pesto_model* m, int64_t F, int64_t n_atoms, const float* X, doubl
     if (rc == 0) {
         const int* off = bf.ptr<const int>(iO);
         const int* blk = bf.ptr<const int>(iB);
-        hipLaunchKernelGGL(k_dssp_gather, dim3(blocks(total)), dim3(NT), 0, bf.stm, total, (int)R_total, n_struct, (size_t)n_atoms, off,
+        hipLaunchKernelGGL(k_dssp_gather, dim3(blocks(total, NT)), dim3(NT), 0, bf.stm, total, (int)R_total, n_struct, (size_t)n_atoms, off,
                            bf.ptr<const float>(iX), scale, bf.ptr<const int>(iT), bf.ptr<const unsigned char>(iPr), bf.ptr<const int>(iCh),
                            bf.ptr<double>(iBB), bf.ptr<unsigned char>(iFl), bf.ptr<int>(iBrk));
         const dim3 pg((unsigned)((size_t)F * n_blk));

@@ -609,7 +609,8 @@ int pesto_pca(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* 
     const int iMo = bf.output(mean_out, (size_t)s.m * 4), iRo = bf.output(resid_out, (size_t)k * 8);
     const int iXp = bf.scratch((size_t)F * s.mp * 4), iMean = bf.scratch((size_t)s.mp * 8), iSq = bf.scratch((size_t)s.mp * 8);
     const size_t vec = (size_t)s.mp * TS * 8;
-    const int iQ = bf.scratch(vec), iY = bf.scratch(vec), iXv = bf.scratch(vec), iZ = bf.scratch(vec), iTmp = bf.scratch(vec);
+    // the block vectors' rows from m on are read as K padding by DQ: Q and X zero once, never written
+    const int iQ = bf.scratch(vec, 0), iY = bf.scratch(vec), iXv = bf.scratch(vec, 0), iZ = bf.scratch(vec), iTmp = bf.scratch(vec);
     const int iP = bf.scratch((size_t)s.Fp * TS * 8), iPart = bf.scratch(s.partial_doubles() * 8);
     const int iT = bf.scratch(TS * TS * 8), iV = bf.scratch(TS * TS * 8), iTh = bf.scratch(TS * 8), iSv = bf.scratch(TS * 8);
     const int iThK = bf.scratch(TS * 8), iRsK = bf.scratch(TS * 8);
@@ -618,9 +619,6 @@ int pesto_pca(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* 
     int rc = bf.upload();
     DynState state{};
     if (rc == 0) rc = hip_ok(hipFuncSetAttribute((const void*)k_dyn_jacobi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JACOBI_LDS), "pca");
-    // the block vectors' rows from m on are read as K padding by DQ: zero once, never written
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<char>(iQ), 0, vec, bf.stm), "pca");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<char>(iXv), 0, vec, bf.stm), "pca");
     if (rc == 0) {
         hipStream_t stm = bf.stm;
         DynState* st = bf.ptr<DynState>(iSt);
@@ -649,7 +647,7 @@ int pesto_pca(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* 
                                    bf.ptr<double>(iRsK), st);
                 launch_ortho(stm, s, a, Z, Tmp, Q, part, T, V, sv);          // the next block
             }
-            if ((rc = bf.read(iSt, &state, sizeof state)) == 0) rc = hip_ok(hipStreamSynchronize(stm), "pca");
+            rc = bf.verdict(iSt, &state, sizeof state, "pca");
         }
         if (rc == 0) {
             Mma b = a;
@@ -683,9 +681,8 @@ int pesto_project(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const flo
     const int iCi = bf.input(components, (size_t)k * s.m * 8), iPr = bf.output(proj_out, (size_t)F * k * 4);
     const int iXp = bf.scratch((size_t)F * s.mp * 4), iMean = bf.scratch((size_t)s.mp * 8), iSq = bf.scratch((size_t)s.mp * 8);
     const size_t vec = (size_t)s.mp * TS * 8;
-    const int iB = bf.scratch(vec), iP = bf.scratch((size_t)s.Fp * TS * 8), iPart = bf.scratch((size_t)s.dq.S * s.Fp * TS * 8);
+    const int iB = bf.scratch(vec, 0), iP = bf.scratch((size_t)s.Fp * TS * 8), iPart = bf.scratch((size_t)s.dq.S * s.Fp * TS * 8);
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<char>(iB), 0, vec, bf.stm), "project");
     if (rc == 0) {
         hipLaunchKernelGGL(k_dyn_mean, dim3((unsigned)(s.mp / MG)), dim3(NT), 0, bf.stm, (int)F, (int)N, (int)s.m, (int)s.mp, bf.ptr<const float>(iX),
                            sel ? bf.ptr<const int>(iS) : nullptr, bf.ptr<const float>(iMi), bf.ptr<float>(iXp), bf.ptr<double>(iMean), bf.ptr<double>(iSq));

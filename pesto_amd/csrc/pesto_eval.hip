@@ -151,7 +151,6 @@ void launch_contact_labels(hipStream_t st, int n_total, int n_struct, const int*
                            const unsigned char* receptor, const unsigned* pmask, int n_res, float r_thr, unsigned* labels, unsigned char* ties,
                            CellGrid* g, int* cell_cnt, int* cell_cur, int* cell_of, float4* sorted, int2* sorted_sm, int* err) {
     const int nb = (n_total + 255) / 256;
-    (void)hipMemsetAsync(labels, 0, (size_t)n_res * sizeof(unsigned), st);
     hipLaunchKernelGGL(k_grid_setup, dim3(n_struct), dim3(256), 0, st, n_struct, offsets, X, r_thr, g, cell_cnt);
     hipLaunchKernelGGL(k_grid_count<LblNoCheck>, dim3(nb), dim3(256), 0, st, n_total, n_struct, offsets, X, (const CellGrid*)g, cell_cnt, cell_of,
                        LblNoCheck{});
@@ -187,12 +186,11 @@ int pesto_interface_labels(pesto_model* m, int64_t n_total, int32_t n_struct, co
     Buffers bf(ptr_kind, stream);
     const int iOff = bf.table(struct_offsets, ((size_t)n_struct + 1) * 4), iX = bf.input(X, n * 12), iS = bf.input(subunit, n * 4),
               iR = bf.input(residue, n * 4), iT = bf.input(receptor, n), iM = bf.input(partner_mask, n * 4);
-    const int iL = bf.output(labels_out, (size_t)n_res * 4), iTi = bf.output(ties_out, n);
-    const int iErr = bf.scratch(4), iG = bf.scratch((size_t)n_struct * sizeof(CellGrid)), iCnt = bf.scratch(cells * 4), iCur = bf.scratch(cells * 4),
+    const int iL = bf.output(labels_out, (size_t)n_res * 4, 0), iTi = bf.output(ties_out, n);
+    const int iErr = bf.scratch(4, 0), iG = bf.scratch((size_t)n_struct * sizeof(CellGrid)), iCnt = bf.scratch(cells * 4), iCur = bf.scratch(cells * 4),
               iCell = bf.scratch(n * 4), iSort = bf.scratch(n * 16), iSm = bf.scratch(n * 8);
     int err = 0;
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iErr), 0, 4, bf.stm), "interface_labels");
     if (rc == 0) {
         launch_contact_labels(bf.stm, (int)n_total, n_struct, bf.ptr<const int>(iOff), bf.ptr<const float>(iX), bf.ptr<const int>(iS),
                               bf.ptr<const int>(iR), bf.ptr<const unsigned char>(iT), bf.ptr<const unsigned>(iM), (int)n_res, r_thr,

@@ -276,8 +276,6 @@ int table_errors(int err) {
     return 0;
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
-
 }  // namespace
 }  // namespace pesto
 
@@ -300,36 +298,25 @@ int pesto_frame_hbonds(pesto_model* m, int64_t F, int64_t N, int64_t P, int64_t 
     Buffers bf(ptr_kind, stream);
     const int iX = bf.input(xyz, (size_t)F * N * 12), iDh = bf.input(dh, (size_t)P * 8), iAc = bf.input(acc, (size_t)A * 4), iG = bf.input(group, (size_t)N);
     const int iO = bf.output(offsets_out, ((size_t)F + 1) * 8), iT = bf.partial(triplets_out, C * 12), iD = bf.partial(d_out, C * 4);
-    const int iSt = bf.scratch(sizeof(ListState)), iCnt = bf.scratch((size_t)F * P * 4), iTot = bf.scratch((size_t)F * 4);
+    const int iSt = bf.scratch(sizeof(ListState), 0), iCnt = bf.scratch((size_t)F * P * 4, 0), iTot = bf.scratch((size_t)F * 4);
     ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<ListState>(iSt), 0, sizeof(ListState), bf.stm), "frame_hbonds");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iCnt), 0, (size_t)F * P * 4, bf.stm), "frame_hbonds");
     if (rc == 0) {
         const dim3 grid((unsigned)(F * tiles));
         const float* X = bf.ptr<const float>(iX);
         const int *pdh = bf.ptr<const int>(iDh), *pac = bf.ptr<const int>(iAc);
         const signed char* pg = bf.ptr<const signed char>(iG);
         ListState* st = bf.ptr<ListState>(iSt);
-        hipLaunchKernelGGL(k_hb_check, dim3(blocks((size_t)(2 * P + A))), dim3(NT), 0, bf.stm, (int)N, (int)P, (int)A, pdh, pac, st);
+        hipLaunchKernelGGL(k_hb_check, dim3(blocks((size_t)(2 * P + A), NT)), dim3(NT), 0, bf.stm, (int)N, (int)P, (int)A, pdh, pac, st);
         hipLaunchKernelGGL(k_hb_pairs<false>, grid, dim3(NT), 0, bf.stm, (int)N, (int)P, (int)A, (int)tiles, X, pdh, pac, pg, s_star, scale, cos2_angle,
                            bf.ptr<int>(iCnt), (const long long*)nullptr, (const ListState*)st, (int*)nullptr, (float*)nullptr);
-        hipLaunchKernelGGL(k_frame_scan<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)P, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
-        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(LIST_SCAN_NT), 0, bf.stm, (int)F, bf.ptr<const int>(iTot), bf.ptr<long long>(iO), (long long)cap, st);
+        list_scan<NT>(bf, (int)F, (int)P, iCnt, iTot, iO, (long long)cap, iSt);
         hipLaunchKernelGGL(k_hb_pairs<true>, grid, dim3(NT), 0, bf.stm, (int)N, (int)P, (int)A, (int)tiles, X, pdh, pac, pg, s_star, scale, cos2_angle,
                            bf.ptr<int>(iCnt), bf.ptr<const long long>(iO), (const ListState*)st, bf.ptr<int>(iT), bf.ptr<float>(iD));
-        rc = hip_ok(hipGetLastError(), "frame_hbonds: launch failed");
     }
     // the one synchronisation for sizing: the count
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(ListState));
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "frame_hbonds: stream synchronisation failed");
-    if (rc == 0 && !hs.err) {
-        sizes_out[0] = hs.K;
-        if (hs.fits) {
-            rc = bf.fetch(iT, (size_t)hs.K * 12);
-            if (rc == 0) rc = bf.fetch(iD, (size_t)hs.K * 4);
-        }
-    }
+    if (rc == 0) rc = bf.verdict(iSt, &hs, sizeof hs, "frame_hbonds");
+    if (rc == 0 && !hs.err) rc = list_tail(bf, hs, sizes_out, {{iT, 12}, {iD, 4}});
     rc = bf.finish(rc, "frame_hbonds");
     return rc ? rc : table_errors(hs.err);
 }
@@ -349,35 +336,24 @@ int pesto_hbond_occupancy(pesto_model* m, int64_t F, int64_t N, int64_t P, int64
     Buffers bf(ptr_kind, stream);
     const int iX = bf.input(xyz, (size_t)F * N * 12), iDh = bf.input(dh, (size_t)P * 8), iAc = bf.input(acc, (size_t)A * 4);
     const int iT = bf.partial(triplets_out, C * 12), iN = bf.partial(counts_out, C * 4);
-    const int iSt = bf.scratch(sizeof(ListState)), iCnt = bf.scratch((size_t)P * S * 4), iTot = bf.scratch((size_t)P * 4),
+    const int iSt = bf.scratch(sizeof(ListState), 0), iCnt = bf.scratch((size_t)P * S * 4, 0), iTot = bf.scratch((size_t)P * 4),
               iO = bf.scratch(((size_t)P + 1) * 8);
     ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<ListState>(iSt), 0, sizeof(ListState), bf.stm), "hbond_occupancy");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iCnt), 0, (size_t)P * S * 4, bf.stm), "hbond_occupancy");
     if (rc == 0) {
         const dim3 grid((unsigned)(tiles * S));
         const float* X = bf.ptr<const float>(iX);
         const int *pdh = bf.ptr<const int>(iDh), *pac = bf.ptr<const int>(iAc);
         ListState* st = bf.ptr<ListState>(iSt);
-        hipLaunchKernelGGL(k_hb_check, dim3(blocks((size_t)(2 * P + A))), dim3(NT), 0, bf.stm, (int)N, (int)P, (int)A, pdh, pac, st);
+        hipLaunchKernelGGL(k_hb_check, dim3(blocks((size_t)(2 * P + A), NT)), dim3(NT), 0, bf.stm, (int)N, (int)P, (int)A, pdh, pac, st);
         hipLaunchKernelGGL(k_hb_occupancy<false>, grid, dim3(NT), 0, bf.stm, (int)F, (int)N, (int)P, (int)A, (int)S, X, pdh, pac, s_star, cos2_angle, freq,
                            bf.ptr<int>(iCnt), (const long long*)nullptr, (const ListState*)st, (int*)nullptr, (int*)nullptr);
-        hipLaunchKernelGGL(k_frame_scan<NT>, dim3((unsigned)P), dim3(NT), 0, bf.stm, (int)S, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
-        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(LIST_SCAN_NT), 0, bf.stm, (int)P, bf.ptr<const int>(iTot), bf.ptr<long long>(iO), (long long)cap, st);
+        list_scan<NT>(bf, (int)P, (int)S, iCnt, iTot, iO, (long long)cap, iSt);
         hipLaunchKernelGGL(k_hb_occupancy<true>, grid, dim3(NT), 0, bf.stm, (int)F, (int)N, (int)P, (int)A, (int)S, X, pdh, pac, s_star, cos2_angle, freq,
                            bf.ptr<int>(iCnt), bf.ptr<const long long>(iO), (const ListState*)st, bf.ptr<int>(iT), bf.ptr<int>(iN));
-        rc = hip_ok(hipGetLastError(), "hbond_occupancy: launch failed");
     }
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(ListState));
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "hbond_occupancy: stream synchronisation failed");
-    if (rc == 0 && !hs.err) {
-        sizes_out[0] = hs.K;
-        if (hs.fits) {
-            rc = bf.fetch(iT, (size_t)hs.K * 12);
-            if (rc == 0) rc = bf.fetch(iN, (size_t)hs.K * 4);
-        }
-    }
+    if (rc == 0) rc = bf.verdict(iSt, &hs, sizeof hs, "hbond_occupancy");
+    if (rc == 0 && !hs.err) rc = list_tail(bf, hs, sizes_out, {{iT, 12}, {iN, 4}});
     rc = bf.finish(rc, "hbond_occupancy");
     return rc ? rc : table_errors(hs.err);
 }
@@ -393,22 +369,20 @@ int pesto_unwrap_pbc(pesto_model* m, int64_t F, int64_t N, int64_t M, const floa
     const int iX = bf.input(xyz, (size_t)F * N * 12), iL = bf.input(unitcell_lengths, (size_t)F * 12), iP = bf.input(perm, (size_t)N * 4),
               iOf = bf.table(mol_off, ((size_t)M + 1) * 4), iMs = bf.input(masses, (size_t)N * 8);
     const int iY = bf.output(xyz_out, (size_t)F * N * 12), iIm = bf.output(image_out, (size_t)F * M * 4);
-    const int iSt = bf.scratch(sizeof(ListState)), iCm = bf.scratch((size_t)F * M * 24), iSeen = bf.scratch((size_t)N * 4);
+    const int iSt = bf.scratch(sizeof(ListState), 0), iCm = bf.scratch((size_t)F * M * 24), iSeen = bf.scratch((size_t)N * 4, 0);
     ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<ListState>(iSt), 0, sizeof(ListState), bf.stm), "unwrap_pbc");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSeen), 0, (size_t)N * 4, bf.stm), "unwrap_pbc");
     if (rc == 0) {
         const dim3 grid((unsigned)(F * M));
         ListState* st = bf.ptr<ListState>(iSt);
-        hipLaunchKernelGGL(k_uw_check, dim3(blocks((size_t)N)), dim3(NT), 0, bf.stm, (int)N, bf.ptr<const int>(iP), bf.ptr<int>(iSeen), st);
+        hipLaunchKernelGGL(k_uw_check, dim3(blocks((size_t)N, NT)), dim3(NT), 0, bf.stm, (int)N, bf.ptr<const int>(iP), bf.ptr<int>(iSeen), st);
         hipLaunchKernelGGL(k_uw_com, grid, dim3(NT), 0, bf.stm, (int)N, (int)M, bf.ptr<const float>(iX), bf.ptr<const int>(iP), bf.ptr<const int>(iOf),
                            bf.ptr<const double>(iMs), (const ListState*)st, bf.ptr<double>(iCm));
         hipLaunchKernelGGL(k_uw_shift, grid, dim3(NT), 0, bf.stm, (int)N, (int)M, bf.ptr<const float>(iX), bf.ptr<const float>(iL), bf.ptr<const int>(iP),
                            bf.ptr<const int>(iOf), bf.ptr<const double>(iCm), (const ListState*)st, bf.ptr<float>(iY), bf.ptr<int>(iIm));
-        rc = hip_ok(hipGetLastError(), "unwrap_pbc: launch failed");
     }
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof(ListState));
+    // (decoded after finish(), whose synchronisation brings it)
+    if (rc == 0) rc = bf.read(iSt, &hs, sizeof hs);
     rc = bf.finish(rc, "unwrap_pbc");
     if (rc == 0 && (hs.err & ERR_PERM)) rc = fail(PESTO_ERR_INVALID, "perm: atom indices must lie in [0, N)");
     if (rc == 0 && (hs.err & ERR_DUP)) rc = fail(PESTO_ERR_INVALID, "perm: every atom must be named once (an index is repeated)");

@@ -272,8 +272,6 @@ __global__ __launch_bounds__(NT) void k_lddt_final(int n_struct, int R, int T, c
 }
 
 // ---- host side
-unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
-
 // the error of a refused call from the check kernel's bits (0: none)
 int index_error(int err, const char* what) {
     if (err & ERR_RES) return fail(PESTO_ERR_INVALID, "%s: res_of_atom must lie in [0, R) (lddt_pairs: must not be negative)", what);
@@ -316,16 +314,17 @@ ListScratch list_scratch(Buffers& bf, size_t n, size_t n_struct) {
     return ls;
 }
 
-// the grid, the count pass and the scan: off[0 .. N] and K (read back; the stream is synchronised)
+// the grid, the count pass and the scan: off[0 .. N] (item iO) and K (read back; the stream is synchronised)
 int list_count(Buffers& bf, const ListScratch& ls, int N, int n_struct, const int* offs, const float* ref, const int* res, const int* chain,
-               const unsigned char* sel, int mode, float r_incl, float scale, float s_star, long long* off, ListState* st, long long* K, const char* what) {
-    const int nb = (int)blocks((size_t)N);
+               const unsigned char* sel, int mode, float r_incl, float scale, float s_star, int iO, int iSt, long long* K, const char* what) {
+    const int nb = (int)blocks((size_t)N, NT);
     CellGrid* g = bf.ptr<CellGrid>(ls.iG);
     int* cell_cnt = bf.ptr<int>(ls.iCnt);
     float* clean = bf.ptr<float>(ls.iClean);
     unsigned char* keep = bf.ptr<unsigned char>(ls.iKeep);
     hipLaunchKernelGGL(k_lddt_anchor, dim3(n_struct), dim3(NT), 0, bf.stm, offs, ref, bf.ptr<int>(ls.iAnchor));
-    hipLaunchKernelGGL(k_lddt_clean, dim3(nb), dim3(NT), 0, bf.stm, N, n_struct, offs, (const int*)bf.ptr<int>(ls.iAnchor), ref, res, sel, clean, keep, st);
+    hipLaunchKernelGGL(k_lddt_clean, dim3(nb), dim3(NT), 0, bf.stm, N, n_struct, offs, (const int*)bf.ptr<int>(ls.iAnchor), ref, res, sel, clean, keep,
+                       bf.ptr<ListState>(iSt));
     ref = clean;
     hipLaunchKernelGGL(k_grid_setup, dim3(n_struct), dim3(256), 0, bf.stm, n_struct, offs, ref, r_incl / scale, g, cell_cnt);
     hipLaunchKernelGGL(k_grid_count<NoCheck>, dim3(nb), dim3(256), 0, bf.stm, N, n_struct, offs, ref, (const CellGrid*)g, cell_cnt,
@@ -337,12 +336,9 @@ int list_count(Buffers& bf, const ListScratch& ls, int N, int n_struct, const in
     hipLaunchKernelGGL(k_lddt_list<false>, dim3(nb), dim3(NT), 0, bf.stm, N, n_struct, offs, (const CellGrid*)g, (const int*)cell_cnt,
                        (const float4*)bf.ptr<float4>(ls.iSort), (const int2*)bf.ptr<int2>(ls.iMeta), mode, s_star, scale, bf.ptr<int>(ls.iRow),
                        (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(LIST_SCAN_NT), 0, bf.stm, N, (const int*)bf.ptr<int>(ls.iRow), off,
-                       (long long)PESTO_LDDT_MAX_ENTRIES, st);
-    if (int rc = hip_ok(hipGetLastError(), what)) return rc;
+    list_offsets(bf, N, ls.iRow, iO, (long long)PESTO_LDDT_MAX_ENTRIES, iSt);
     ListState h{};
-    if (int rc = hip_ok(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, bf.stm), what)) return rc;
-    if (int rc = hip_ok(hipStreamSynchronize(bf.stm), what)) return rc;
+    if (int rc = bf.verdict(iSt, &h, sizeof h, what)) return rc;
     *K = h.K;
     if (h.err) return index_error(h.err, what);
     return 0;
@@ -351,21 +347,19 @@ int list_count(Buffers& bf, const ListScratch& ls, int N, int n_struct, const in
 // the fill pass into jn / dref (K entries, sized by the caller)
 void list_fill(Buffers& bf, const ListScratch& ls, int N, int n_struct, const int* offs, int mode, float s_star, float scale,
                const long long* off, int* jn, float* dref) {
-    hipLaunchKernelGGL(k_lddt_list<true>, dim3(blocks((size_t)N)), dim3(NT), 0, bf.stm, N, n_struct, offs, (const CellGrid*)bf.ptr<CellGrid>(ls.iG),
+    hipLaunchKernelGGL(k_lddt_list<true>, dim3(blocks((size_t)N, NT)), dim3(NT), 0, bf.stm, N, n_struct, offs, (const CellGrid*)bf.ptr<CellGrid>(ls.iG),
                        (const int*)bf.ptr<int>(ls.iCnt), (const float4*)bf.ptr<float4>(ls.iSort), (const int2*)bf.ptr<int2>(ls.iMeta), mode,
                        s_star, scale, (int*)nullptr, off, jn, dref);
 }
 
-// the check kernel and its verdict, read before anything else is launched
+// the check kernel and its verdict (item iSt, declared cleared), read before anything else is launched
 int run_check(Buffers& bf, int N, int R, int n_struct, long long K, const int* offs, const int* rso, const int* res, const int* perm,
-              const int* roff, const long long* off, const int* jn, ListState* st, const char* what) {
-    if (int rc = hip_ok(hipMemsetAsync(st, 0, sizeof(ListState), bf.stm), what)) return rc;
+              const int* roff, const long long* off, const int* jn, int iSt, const char* what) {
     const size_t n = std::max<size_t>((size_t)N + 1, off ? (size_t)K : 0);
-    hipLaunchKernelGGL(k_lddt_check, dim3(blocks(n)), dim3(NT), 0, bf.stm, N, R, n_struct, K, offs, rso, res, perm, roff, off, jn, st);
-    if (int rc = hip_ok(hipGetLastError(), what)) return rc;
+    hipLaunchKernelGGL(k_lddt_check, dim3(blocks(n, NT)), dim3(NT), 0, bf.stm, N, R, n_struct, K, offs, rso, res, perm, roff, off, jn,
+                       bf.ptr<ListState>(iSt));
     ListState h{};
-    if (int rc = hip_ok(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, bf.stm), what)) return rc;
-    if (int rc = hip_ok(hipStreamSynchronize(bf.stm), what)) return rc;
+    if (int rc = bf.verdict(iSt, &h, sizeof h, what)) return rc;
     return index_error(h.err, what);
 }
 
@@ -391,15 +385,14 @@ int pesto_lddt_pairs(pesto_model* m, int64_t N, int32_t n_struct, const int32_t*
     const int iOff = bf.table(struct_offsets, ((size_t)n_struct + 1) * 4), iY = bf.input(xyz_ref, n * 12), iR = bf.input(res_of_atom, n * 4),
               iC = bf.input(chain_of_atom, n * 4), iS = bf.input(sel, n);
     const int iO = bf.output(offsets_out, (n + 1) * 8), iJ = bf.partial(j_out, (size_t)capacity * 4), iD = bf.partial(d_out, (size_t)capacity * 4);
-    const int iSt = bf.scratch(sizeof(ListState));
+    const int iSt = bf.scratch(sizeof(ListState), 0);
     const ListScratch ls = list_scratch(bf, n, (size_t)n_struct);
     long long K = 0;
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<ListState>(iSt), 0, sizeof(ListState), bf.stm), "lddt_pairs");
     // (res_of_atom, chain_of_atom and sel are only compared here: nothing to validate)
     if (rc == 0)
         rc = list_count(bf, ls, (int)N, n_struct, bf.ptr<const int>(iOff), bf.ptr<const float>(iY), bf.ptr<const int>(iR), bf.ptr<const int>(iC),
-                        bf.ptr<const unsigned char>(iS), mode, r_incl, fscale, s_star, bf.ptr<long long>(iO), bf.ptr<ListState>(iSt), &K, "lddt_pairs");
+                        bf.ptr<const unsigned char>(iS), mode, r_incl, fscale, s_star, iO, iSt, &K, "lddt_pairs");
     if (rc == 0) {
         *n_pairs_out = K;
         if (K > PESTO_LDDT_MAX_ENTRIES) rc = fail(PESTO_ERR_INVALID, "lddt_pairs: %lld reference pairs, at most 2^30 per call", K);
@@ -451,7 +444,7 @@ int pesto_lddt(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int
               iDi = bf.input(given ? d_in : nullptr, (size_t)K_in * 4);
     const int iSc = bf.output(score_out, (size_t)F * n_struct * 4), iRe = bf.output(residue_out, (size_t)F * nr * 4),
               iPr = bf.output(preserved_out, (size_t)F * nr * T * 4), iTo = bf.output(total_out, nr * 4);
-    const int iSt = bf.scratch(sizeof(ListState)), iNp = bf.scratch((size_t)n_struct * 8), iOs = bf.scratch(given ? 0 : (n + 1) * 8);
+    const int iSt = bf.scratch(sizeof(ListState), 0), iNp = bf.scratch((size_t)n_struct * 8), iOs = bf.scratch(given ? 0 : (n + 1) * 8);
     ListScratch ls{};
     if (!given) ls = list_scratch(bf, n, (size_t)n_struct);
     char* list = nullptr;               // the call's own list: K entries, known only after the count pass
@@ -464,10 +457,10 @@ int pesto_lddt(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int
     long long K = given ? (long long)K_in : 0;
     if (rc == 0)
         rc = run_check(bf, (int)N, (int)R, n_struct, K, offs, rso, bf.ptr<const int>(iR), bf.ptr<const int>(iPm), bf.ptr<const int>(iRo),
-                       given ? off : nullptr, jn, bf.ptr<ListState>(iSt), "lddt");
+                       given ? off : nullptr, jn, iSt, "lddt");
     if (rc == 0 && !given) {
         rc = list_count(bf, ls, (int)N, n_struct, offs, bf.ptr<const float>(iY), bf.ptr<const int>(iR), bf.ptr<const int>(iC),
-                        bf.ptr<const unsigned char>(iS), mode, r_incl, fscale, s_star, bf.ptr<long long>(iOs), bf.ptr<ListState>(iSt), &K, "lddt");
+                        bf.ptr<const unsigned char>(iS), mode, r_incl, fscale, s_star, iOs, iSt, &K, "lddt");
         if (rc == 0 && K > PESTO_LDDT_MAX_ENTRIES) {
             n_pairs_out[0] = K;                                         // (the caller tells this refusal by it)
             rc = fail(PESTO_ERR_INVALID, "lddt: %lld reference pairs, at most 2^30 per call", K);
@@ -483,7 +476,7 @@ int pesto_lddt(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int
         }
     }
     if (rc == 0) {
-        hipLaunchKernelGGL(k_lddt_total, dim3(blocks(nr + (size_t)n_struct)), dim3(NT), 0, bf.stm, (int)R, n_struct, offs, bf.ptr<const int>(iPm),
+        hipLaunchKernelGGL(k_lddt_total, dim3(blocks(nr + (size_t)n_struct, NT)), dim3(NT), 0, bf.stm, (int)R, n_struct, offs, bf.ptr<const int>(iPm),
                            bf.ptr<const int>(iRo), off, bf.ptr<int>(iTo), bf.ptr<long long>(iNp));
         const int groups = (int)((R + NW - 1) / NW);
         const long long n_items = (long long)F * groups;
@@ -493,7 +486,6 @@ int pesto_lddt(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int
                            bf.ptr<const int>(iRo), off, jn, dref, bf.ptr<int>(iPr));
         hipLaunchKernelGGL(k_lddt_final, dim3((unsigned)(F * n_struct)), dim3(NT), 0, bf.stm, n_struct, (int)R, (int)T, rso,
                            (const int*)bf.ptr<int>(iTo), (const int*)bf.ptr<int>(iPr), bf.ptr<float>(iRe), bf.ptr<float>(iSc));
-        rc = hip_ok(hipGetLastError(), "lddt: launch failed");
     }
     if (rc == 0) rc = bf.read(iNp, n_pairs_out, (size_t)n_struct * 8);
     if (list) (void)hipFreeAsync(list, bf.stm);

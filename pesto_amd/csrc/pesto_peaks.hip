@@ -425,26 +425,22 @@ Source declare_source(Buffers& bf, int64_t F, int32_t d, const float* X, const f
     s.iIn = s.matrix ? bf.input(D, (size_t)(F * F) * 4) : bf.input(X, (size_t)F * d * 4);
     s.iIdx = bf.input(idx, (size_t)n * 4);
     s.iP = s.matrix ? -1 : bf.scratch((size_t)n * s.DP * 4);
-    s.iSt = bf.scratch(ST_WORDS * 4);
+    s.iSt = bf.scratch(ST_WORDS * 4, 0);
     return s;
 }
-
-unsigned blocks(int n) { return (unsigned)((n + NT - 1) / NT); }
 
 // the checks made on the device, and the points gathered: the one early synchronisation of a call, so that a refused call writes nothing
 int validate_source(Buffers& bf, const Source& s, bool has_idx, const char* what) {
     int* st = bf.ptr<int>(s.iSt);
     const int* idx = has_idx ? bf.ptr<const int>(s.iIdx) : nullptr;
-    if (int rc = hip_ok(hipMemsetAsync(st, 0, ST_WORDS * 4, bf.stm), what)) return rc;
     if (s.matrix) {
         hipLaunchKernelGGL(k_pk_check_matrix, dim3((unsigned)s.F), dim3(NT), 0, bf.stm, s.F, bf.ptr<const float>(s.iIn), st);
-        if (idx) hipLaunchKernelGGL(k_pk_check_idx, dim3(blocks(s.n)), dim3(NT), 0, bf.stm, s.F, s.n, idx, st);
+        if (idx) hipLaunchKernelGGL(k_pk_check_idx, dim3(blocks((size_t)s.n, NT)), dim3(NT), 0, bf.stm, s.F, s.n, idx, st);
     } else {
-        hipLaunchKernelGGL(k_pk_gather, dim3(blocks(s.n)), dim3(NT), 0, bf.stm, s.F, s.d, s.DP, s.n, bf.ptr<const float>(s.iIn), idx, bf.ptr<float>(s.iP), st);
+        hipLaunchKernelGGL(k_pk_gather, dim3(blocks((size_t)s.n, NT)), dim3(NT), 0, bf.stm, s.F, s.d, s.DP, s.n, bf.ptr<const float>(s.iIn), idx, bf.ptr<float>(s.iP), st);
     }
     int32_t state[ST_WORDS] = {0, 0, 0, 0};
-    if (int rc = bf.read(s.iSt, state, sizeof state)) return rc;
-    if (int rc = hip_ok(hipStreamSynchronize(bf.stm), what)) return rc;
+    if (int rc = bf.verdict(s.iSt, state, sizeof state, what)) return rc;
     const int e = state[ST_ERR];
     if (e & E_INDEX) return fail(PESTO_ERR_INVALID, "idx: row indices must lie in 0 .. %d", s.F - 1);
     if (e & E_NONFINITE) return fail(PESTO_ERR_INVALID, "%s", s.matrix ? "D has a non-finite entry" : "X has a non-finite coordinate");
@@ -487,14 +483,13 @@ int pesto_weighted_centers(pesto_model* m, int64_t F, int64_t R, const float* Xp
     const int iX = bf.input(Xp, (size_t)F * R * 12), iW = bf.input(PW, (size_t)F * R * 4);
     const int iC = bf.output(centers_out, (size_t)F * 12), iS = bf.output(wsum_out, (size_t)F * 8), iG = bf.output(rg_out, (size_t)F * 4);
     // the results are made in scratch and handed over once the weights are known to be good: a refused call writes nothing
-    const int tC = bf.scratch((size_t)F * 12), tS = bf.scratch((size_t)F * 8), tG = bf.scratch((size_t)F * 4), iSt = bf.scratch(ST_WORDS * 4);
+    const int tC = bf.scratch((size_t)F * 12), tS = bf.scratch((size_t)F * 8), tG = bf.scratch((size_t)F * 4), iSt = bf.scratch(ST_WORDS * 4, 0);
     int rc = bf.upload();
     int32_t state[ST_WORDS] = {0, 0, 0, 0};
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<int>(iSt), 0, ST_WORDS * 4, bf.stm), "weighted_centers");
     if (rc == 0) {
         hipLaunchKernelGGL(k_pk_centers, dim3((unsigned)F), dim3(NT), 0, bf.stm, (int)R, bf.ptr<const float>(iX), bf.ptr<const float>(iW), mode, p_thr,
                            bf.ptr<float>(tC), bf.ptr<double>(tS), bf.ptr<float>(tG), bf.ptr<int>(iSt));
-        if ((rc = bf.read(iSt, state, sizeof state)) == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "weighted_centers");
+        rc = bf.verdict(iSt, state, sizeof state, "weighted_centers");
     }
     if (rc == 0 && (state[ST_ERR] & E_WEIGHT)) rc = fail(PESTO_ERR_INVALID, "W has a negative or non-finite weight");
     if (rc == 0) rc = hip_ok(hipMemcpyAsync(bf.ptr<void>(iC), bf.ptr<void>(tC), (size_t)F * 12, hipMemcpyDeviceToDevice, bf.stm), "weighted_centers");
@@ -513,10 +508,9 @@ int pesto_pair_distance_rank(pesto_model* m, int64_t F, int32_t d, const float* 
     Buffers bf(ptr_kind, stream);
     const Source s = declare_source(bf, F, d, X, D, n, idx);
     const unsigned long long kinit[2] = {(unsigned long long)k, 0ull};
-    const int iK = bf.table(kinit, sizeof kinit), iB = bf.scratch(MAX_BINS * 8);
+    const int iK = bf.table(kinit, sizeof kinit), iB = bf.scratch(MAX_BINS * 8, 0);
     int rc = bf.upload();
     if (rc == 0) rc = validate_source(bf, s, idx != nullptr, "pair_distance_rank");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iB), 0, MAX_BINS * 8, bf.stm), "pair_distance_rank");
     unsigned long long kst[2] = {0ull, 0ull};
     int32_t state[ST_WORDS] = {0, 0, 0, 0};
     if (rc == 0) {
@@ -531,8 +525,7 @@ int pesto_pair_distance_rank(pesto_model* m, int64_t F, int32_t d, const float* 
             launch_pairs(bf, s, idx != nullptr, h);
             hipLaunchKernelGGL(k_pk_select, dim3(1), dim3(NT), 0, bf.stm, bins, dk, nbins[p], shifts[p], bf.ptr<int>(s.iSt));
         }
-        if ((rc = bf.read(iK, kst, sizeof kst)) == 0 && (rc = bf.read(s.iSt, state, sizeof state)) == 0)
-            rc = hip_ok(hipStreamSynchronize(bf.stm), "pair_distance_rank");
+        if ((rc = bf.read(iK, kst, sizeof kst)) == 0) rc = bf.verdict(s.iSt, state, sizeof state, "pair_distance_rank");      // (one synchronisation brings both)
     }
     if (rc == 0 && (state[ST_ERR] & E_RANK)) rc = fail(PESTO_ERR_STATE, "the histogram does not hold the rank");
     if (rc == 0) *dist_out = from_bits((uint32_t)kst[1]);
@@ -587,25 +580,25 @@ int pesto_density_peaks(pesto_model* m, int64_t F, int32_t d, const float* X, co
             Rank<0> pick; pick.val = gamma; pick.flag = flag; pick.cidx = cidx; pick.centers = centers; pick.state = st; pick.K = n_clusters;
             launch_rank(bf, nn, pick);
         } else {
-            hipLaunchKernelGGL(k_pk_flag, dim3(blocks(nn)), dim3(NT), 0, bf.stm, nn, rho, delta, rho_min, delta_min, st, flag);
+            hipLaunchKernelGGL(k_pk_flag, dim3(blocks((size_t)nn, NT)), dim3(NT), 0, bf.stm, nn, rho, delta, rho_min, delta_min, st, flag);
         }
         Rank<1> order; order.val = rho; order.flag = flag; order.cidx = cidx; order.centers = centers; order.state = st; order.K = 0;
         launch_rank(bf, nn, order);
         int* pa = bf.ptr<int>(iPa);
         int* pb = bf.ptr<int>(iPb);
-        hipLaunchKernelGGL(k_pk_parent, dim3(blocks(nn)), dim3(NT), 0, bf.stm, nn, flag, nh, pa);
+        hipLaunchKernelGGL(k_pk_parent, dim3(blocks((size_t)nn, NT)), dim3(NT), 0, bf.stm, nn, flag, nh, pa);
         for (int reach = 1; reach < nn; reach *= 2) {       // ceil(log2 n) rounds: a chain has at most n - 1 steps
-            hipLaunchKernelGGL(k_pk_jump, dim3(blocks(nn)), dim3(NT), 0, bf.stm, nn, pa, pb);
+            hipLaunchKernelGGL(k_pk_jump, dim3(blocks((size_t)nn, NT)), dim3(NT), 0, bf.stm, nn, pa, pb);
             int* t = pa; pa = pb; pb = t;
         }
         rc = hip_ok(hipMemsetAsync(sizes, 0, N * 4, bf.stm), "density_peaks");
         if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iRb), 0, N * 8, bf.stm), "density_peaks");
         if (rc == 0) {
-            hipLaunchKernelGGL(k_pk_label, dim3(blocks(nn)), dim3(NT), 0, bf.stm, nn, pa, cidx, labels, sizes);
+            hipLaunchKernelGGL(k_pk_label, dim3(blocks((size_t)nn, NT)), dim3(NT), 0, bf.stm, nn, pa, cidx, labels, sizes);
             Border bd; bd.dc = dc; bd.rho = rho; bd.labels = labels; bd.rhob = bf.ptr<unsigned long long>(iRb);
             launch_pairs(bf, s, has_idx, bd);
-            hipLaunchKernelGGL(k_pk_halo, dim3(blocks(nn)), dim3(NT), 0, bf.stm, nn, rho, labels, bf.ptr<const double>(iRb), bf.ptr<uint8_t>(iHalo));
-            if ((rc = bf.read(s.iSt, state, sizeof state)) == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "density_peaks");
+            hipLaunchKernelGGL(k_pk_halo, dim3(blocks((size_t)nn, NT)), dim3(NT), 0, bf.stm, nn, rho, labels, bf.ptr<const double>(iRb), bf.ptr<uint8_t>(iHalo));
+            rc = bf.verdict(s.iSt, state, sizeof state, "density_peaks");
         }
     }
     const int C = state[ST_CENTRES];

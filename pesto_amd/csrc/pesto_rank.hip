@@ -32,7 +32,7 @@ static_assert(RK_TILE == RADIX_TILE && RK_NT * RADIX_ITEMS == RK_TILE, "the tile
 // the device state of one call: the list protocol's counters (err bit 0: a non-finite p), the number of keys (k_rank_keys writes it
 // for the sort, which reads its length on the device) and the sort's own state
 struct RankState {
-    ListState ls;
+    ListState ls;       // (first: the item of a RankState is the call's ListState to list_offsets)
     int n;
     RadixState rs;
 };
@@ -320,7 +320,7 @@ void rank_declare(Buffers& bf, const int32_t* res_offsets, const uint8_t* y, con
     rk.iOff = bf.table(res_offsets, ((size_t)rk.n_struct + 1) * 4);
     rk.iY = bf.input(y, n);
     rk.iP = bf.input(p, n * 4);
-    rk.iSt = bf.scratch(sizeof(RankState));
+    rk.iSt = bf.scratch(sizeof(RankState), 0);
     rk.iKa = bf.scratch(n * 8);
     rk.iKb = bf.scratch(n * 8);
     rk.iCnt = bf.scratch(radix_counter_bytes(n));
@@ -332,9 +332,8 @@ void rank_declare(Buffers& bf, const int32_t* res_offsets, const uint8_t* y, con
     rk.iY0 = bf.scratch(nc * 4);
 }
 
-// keys -> radix passes -> group ends and the scan of y: 4 + 3 n_pass launches and one memset
+// keys -> radix passes -> group ends and the scan of y: 4 + 3 n_pass launches
 int rank_sort(Buffers& bf, const RankCall& rk, const char* what) {
-    if (int rc = hip_ok(hipMemsetAsync(rk.st(bf), 0, sizeof(RankState), bf.stm), what)) return rc;
     u64 *ka = bf.ptr<u64>(rk.iKa), *kb = bf.ptr<u64>(rk.iKb);
     hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)((rk.n + RK_NT - 1) / RK_NT)), dim3(RK_NT), 0, bf.stm, rk.n, rk.n_class, rk.n_struct,
                        bf.ptr<const int>(rk.iOff), bf.ptr<const unsigned char>(rk.iY), bf.ptr<const float>(rk.iP), ka, rk.st(bf));
@@ -346,7 +345,7 @@ int rank_sort(Buffers& bf, const RankCall& rk, const char* what) {
     hipLaunchKernelGGL(k_rank_points, dim3(rk.n_tiles), dim3(RK_NT), 0, bf.stm, rk.n, (const u64*)ka, (const u64*)kb, rk.n_pass,
                        (const RankState*)rk.st(bf), bf.ptr<const int>(rk.iTy), bf.ptr<const int>(rk.iTg), rk.n_col, bf.ptr<int>(rk.iPos),
                        bf.ptr<int>(rk.iTp), bf.ptr<int>(rk.iC0), bf.ptr<int>(rk.iY0));
-    return hip_ok(hipGetLastError(), what);
+    return bf.launched(what);
 }
 
 // what every kernel after the sort takes, in their order
@@ -408,23 +407,13 @@ int pesto_rank_curves(pesto_model* m, int32_t n_struct, const int32_t* res_offse
         const dim3 grid((unsigned)rk.n_col);
         hipLaunchKernelGGL(k_rank_curve<false>, grid, dim3(RK_NT), 0, bf.stm, rk.n_class, mode, bf.ptr<const int>(rk.iOff), RANK_POINTS(bf, rk),
                            bf.ptr<int>(iN), (const long long*)nullptr, (float*)nullptr, (long long*)nullptr, (long long*)nullptr);
-        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(LIST_SCAN_NT), 0, bf.stm, (int)rk.n_col, bf.ptr<const int>(iN), bf.ptr<long long>(iO),
-                           (long long)capacity, &rk.st(bf)->ls);
+        list_offsets(bf, (int)rk.n_col, iN, iO, (long long)capacity, rk.iSt);
         hipLaunchKernelGGL(k_rank_curve<true>, grid, dim3(RK_NT), 0, bf.stm, rk.n_class, mode, bf.ptr<const int>(rk.iOff), RANK_POINTS(bf, rk),
                            bf.ptr<int>(iN), bf.ptr<const long long>(iO), bf.ptr<float>(iT), bf.ptr<long long>(iTps), bf.ptr<long long>(iFps));
-        rc = hip_ok(hipGetLastError(), "rank_curves: launch failed");
     }
     // the one synchronisation for sizing: the count
-    if (rc == 0) rc = bf.read(rk.iSt, &hs, sizeof hs);
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "rank_curves: stream synchronisation failed");
-    if (rc == 0) {
-        sizes_out[0] = hs.ls.K;
-        if (hs.ls.fits && !(hs.ls.err & 1)) {
-            rc = bf.fetch(iT, (size_t)hs.ls.K * 4);
-            if (rc == 0) rc = bf.fetch(iTps, (size_t)hs.ls.K * 8);
-            if (rc == 0) rc = bf.fetch(iFps, (size_t)hs.ls.K * 8);
-        }
-    }
+    if (rc == 0) rc = bf.verdict(rk.iSt, &hs, sizeof hs, "rank_curves");
+    if (rc == 0) rc = list_tail(bf, hs.ls, sizes_out, {{iT, 4}, {iTps, 8}, {iFps, 8}}, !(hs.ls.err & 1));
     return rank_finish(bf, rc, hs, "rank_curves");
 }
 

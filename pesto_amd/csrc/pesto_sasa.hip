@@ -331,9 +331,6 @@ __global__ __launch_bounds__(NT) void k_sasa_groups(size_t total, int n_total, i
     out[k] = (float)sum;
 }
 
-// ---- host side
-unsigned blocks(size_t n) { return (unsigned)((n + NT - 1) / NT); }
-
 }  // namespace
 }  // namespace pesto
 
@@ -384,11 +381,11 @@ int pesto_sasa(pesto_model* m, int64_t F, int64_t n_total, int32_t n_struct, con
         hipLaunchKernelGGL(k_sasa_sigma, dim3(1), dim3(NT), 0, bf.stm, P, bf.ptr<const float>(iS), bf.ptr<double>(iSig));
         hipLaunchKernelGGL(k_sasa_setup, dim3((unsigned)n_grids), dim3(NT), 0, bf.stm, n_struct, (int)n_total, off, cap, total_cap, x, r,
                            bf.ptr<const double>(iSig), bf.ptr<SasaGrid>(iGr), bf.ptr<int>(iCnt));
-        hipLaunchKernelGGL(k_sasa_count, dim3(blocks(total)), dim3(NT), 0, bf.stm, total, n_struct, (int)n_total, off, cap, total_cap, x, r,
+        hipLaunchKernelGGL(k_sasa_count, dim3(blocks(total, NT)), dim3(NT), 0, bf.stm, total, n_struct, (int)n_total, off, cap, total_cap, x, r,
                            bf.ptr<const SasaGrid>(iGr), bf.ptr<int>(iCnt), bf.ptr<int>(iCell));
         hipLaunchKernelGGL(k_sasa_scan, dim3((unsigned)n_grids), dim3(NT), 0, bf.stm, n_struct, cap, total_cap, bf.ptr<const SasaGrid>(iGr),
                            bf.ptr<int>(iCnt), bf.ptr<int>(iCur));
-        hipLaunchKernelGGL(k_sasa_scatter, dim3(blocks(total)), dim3(NT), 0, bf.stm, total, n_struct, (int)n_total, off, cap, total_cap, x, r,
+        hipLaunchKernelGGL(k_sasa_scatter, dim3(blocks(total, NT)), dim3(NT), 0, bf.stm, total, n_struct, (int)n_total, off, cap, total_cap, x, r,
                            bf.ptr<const int>(iCell), bf.ptr<int>(iCur), bf.ptr<float4>(iSort), bf.ptr<int>(iPos));
         if (dbg & 1) {                                      // timing hook: the grid build alone; the outputs are zeroed
             for (int it : {iC, iA, iQ})
@@ -399,10 +396,10 @@ int pesto_sasa(pesto_model* m, int64_t F, int64_t n_total, int32_t n_struct, con
                                bf.ptr<const int>(iCnt), bf.ptr<const int>(iCell), bf.ptr<const float4>(iSort), bf.ptr<const int>(iPos),
                                (dbg & 2) ? 0 : 1, bf.ptr<int>(iC));
             if (area_out)
-                hipLaunchKernelGGL(k_sasa_area, dim3(blocks(total)), dim3(NT), 0, bf.stm, total, (int)n_total, c0, bf.ptr<const int>(iC), r,
+                hipLaunchKernelGGL(k_sasa_area, dim3(blocks(total, NT)), dim3(NT), 0, bf.stm, total, (int)n_total, c0, bf.ptr<const int>(iC), r,
                                    bf.ptr<float>(iA));
             if (group_out)
-                hipLaunchKernelGGL(k_sasa_groups, dim3(blocks((size_t)F * n_groups)), dim3(NT), 0, bf.stm, (size_t)F * n_groups, (int)n_total,
+                hipLaunchKernelGGL(k_sasa_groups, dim3(blocks((size_t)F * n_groups, NT)), dim3(NT), 0, bf.stm, (size_t)F * n_groups, (int)n_total,
                                    n_groups, c0, bf.ptr<const int>(iC), r, bf.ptr<const int>(iP), bf.ptr<const int>(iG), bf.ptr<float>(iQ));
         }
     }

@@ -1,8 +1,12 @@
 // pesto_scan.h - the scans and searches the analysis groups share: the range of an offsets array that holds an index (struct_of), the
 // one-workgroup exclusive scan (block_scan_exclusive) and the list protocol of the list-valued entry points (count -> scan per frame ->
-// 64-bit offsets -> emit: ListState, k_frame_scan, k_list_offsets).
+// 64-bit offsets -> emit: ListState, k_frame_scan, k_list_offsets on the device; list_scan, list_offsets, list_tail on the host).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <initializer_list>
+
+#include "pesto_call.h"
 
 namespace pesto {
 
@@ -89,6 +93,33 @@ __global__ __launch_bounds__(LIST_SCAN_NT) void k_list_offsets(int F, const int*
         st->K = part[LIST_SCAN_NT - 1];
         st->fits = part[LIST_SCAN_NT - 1] <= cap ? 1 : 0;
     }
+}
+
+// ---- the host half: the scan's launches between the call's count and emit passes, and the list's way back after verdict()
+
+// off[0 .. F] (item iOff), K and whether it fits `cap` (item iSt, a ListState) from the F totals of item iTot
+void list_offsets(Buffers& bf, int F, int iTot, int iOff, long long cap, int iSt) {
+    hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(LIST_SCAN_NT), 0, bf.stm, F, bf.ptr<const int>(iTot), bf.ptr<long long>(iOff), cap,
+                       bf.ptr<ListState>(iSt));
+}
+
+// ... from F frames of n counts each (item iCnt, scanned in place per frame; their totals to item iTot)
+template <int NT>
+void list_scan(Buffers& bf, int F, int n, int iCnt, int iTot, int iOff, long long cap, int iSt) {
+    hipLaunchKernelGGL(k_frame_scan<NT>, dim3((unsigned)F), dim3(NT), 0, bf.stm, n, bf.ptr<int>(iCnt), bf.ptr<int>(iTot));
+    list_offsets(bf, F, iTot, iOff, cap, iSt);
+}
+
+// sizes_out[0] = K; where the list fits (and the caller's own condition `take` holds), the first K entries of every partial output
+// named as {item, bytes per entry}
+struct ListPart { int item; size_t bytes; };
+
+int list_tail(Buffers& bf, const ListState& hs, int64_t* sizes_out, std::initializer_list<ListPart> parts, bool take = true) {
+    sizes_out[0] = hs.K;
+    if (hs.fits && take)
+        for (const ListPart& p : parts)
+            if (int rc = bf.fetch(p.item, (size_t)hs.K * p.bytes)) return rc;
+    return 0;
 }
 
 }  // namespace

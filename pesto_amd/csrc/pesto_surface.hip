@@ -228,8 +228,6 @@ __global__ __launch_bounds__(SF_NT) void k_surf_scored(const int* __restrict__ r
 }
 
 // ------------------------------------------------------------------------------------------------ the host side
-unsigned blocks_of(long long n) { return (unsigned)((n + SF_NT - 1) / SF_NT); }
-
 // offs[0 .. n] from 0 to its total without running backwards (a structure may have no face)
 int check_face_offsets(const int32_t* offs, int32_t n) {
     if (offs[0] != 0) return fail(PESTO_ERR_INVALID, "f_offsets must start at 0");
@@ -283,14 +281,13 @@ int pesto_surface_nearest(pesto_model* m, int32_t n_struct, const int32_t* v_off
     Buffers bf(ptr_kind, stream);
     const int iVo = bf.table(v_offsets, ((size_t)n_struct + 1) * 4), iAo = bf.table(a_offsets, ((size_t)n_struct + 1) * 4),
               iIo = bf.table(item_off.data(), ((size_t)n_struct + 1) * 4), iV = bf.input(vertices, (size_t)V * 12),
-              iX = bf.input(xyz, (size_t)a_offsets[n_struct] * 12), iP = bf.scratch((size_t)V * 8), iI = bf.output(index_out, (size_t)V * 4),
+              iX = bf.input(xyz, (size_t)a_offsets[n_struct] * 12), iP = bf.scratch((size_t)V * 8, 0xff), iI = bf.output(index_out, (size_t)V * 4),
               iD = bf.output(distance_out, (size_t)V * 4);
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iP), 0xff, (size_t)V * 8, bf.stm), "surface_nearest");
     if (rc == 0) {
         hipLaunchKernelGGL(k_surf_nearest, dim3((unsigned)items), dim3(SF_NT), 0, bf.stm, (int)n_struct, (int)slab, bf.ptr<const int>(iIo),
                            bf.ptr<const int>(iVo), bf.ptr<const int>(iAo), bf.ptr<const float>(iV), bf.ptr<const float>(iX), bf.ptr<u64>(iP));
-        hipLaunchKernelGGL(k_surf_unpack, dim3(blocks_of(V)), dim3(SF_NT), 0, bf.stm, V, bf.ptr<const u64>(iP), bf.ptr<int>(iI), bf.ptr<float>(iD));
+        hipLaunchKernelGGL(k_surf_unpack, dim3(blocks((size_t)V, SF_NT)), dim3(SF_NT), 0, bf.stm, V, bf.ptr<const u64>(iP), bf.ptr<int>(iI), bf.ptr<float>(iD));
     }
     return bf.finish(rc, "surface_nearest");
 }
@@ -305,15 +302,13 @@ int pesto_surface_areas(pesto_model* m, int32_t n_struct, const int32_t* v_offse
     if (int rc = begin(m, ptr_kind)) return rc;
     Buffers bf(ptr_kind, stream);
     const int iVo = bf.table(v_offsets, ((size_t)n_struct + 1) * 4), iFo = bf.table(f_offsets, ((size_t)n_struct + 1) * 4),
-              iV = bf.input(vertices, (size_t)V * 12), iF = bf.input(F ? faces : nullptr, (size_t)F * 12), iA = bf.output(area_fixed_out, (size_t)V * 8),
-              iSt = bf.scratch(sizeof(ListState));
+              iV = bf.input(vertices, (size_t)V * 12), iF = bf.input(F ? faces : nullptr, (size_t)F * 12), iA = bf.output(area_fixed_out, (size_t)V * 8, 0),
+              iSt = bf.scratch(sizeof(ListState), 0);
     ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iSt), 0, sizeof(ListState), bf.stm), "surface_areas");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iA), 0, (size_t)V * 8, bf.stm), "surface_areas");
     if (rc == 0) {
         if (F > 0)
-            hipLaunchKernelGGL(k_surf_areas, dim3(blocks_of(F)), dim3(SF_NT), 0, bf.stm, F, (int)n_struct, bf.ptr<const int>(iVo), bf.ptr<const int>(iFo),
+            hipLaunchKernelGGL(k_surf_areas, dim3(blocks((size_t)F, SF_NT)), dim3(SF_NT), 0, bf.stm, F, (int)n_struct, bf.ptr<const int>(iVo), bf.ptr<const int>(iFo),
                                bf.ptr<const float>(iV), bf.ptr<const int>(iF), bf.ptr<long long>(iA), bf.ptr<ListState>(iSt));
         rc = bf.read(iSt, &hs, sizeof hs);
     }
@@ -336,22 +331,18 @@ int pesto_surface_residues(pesto_model* m, int32_t n_struct, const int32_t* v_of
     const int iVo = bf.table(v_offsets, ((size_t)n_struct + 1) * 4), iAo = bf.table(a_offsets, ((size_t)n_struct + 1) * 4),
               iRo = bf.table(r_offsets, ((size_t)n_struct + 1) * 4), iNe = bf.input(nearest, (size_t)V * 4), iAr = bf.input(atom_residue, (size_t)N * 4),
               iAf = bf.input(area_fixed, (size_t)V * 8), iIf = bf.input(iface, (size_t)V), iSc = bf.input(vertex_score, (size_t)V * 4),
-              iN = bf.output(n_vertices_out, (size_t)R * 4), iA = bf.output(area_out, (size_t)R * 8), iIa = bf.output(iface_area_out, (size_t)R * 8),
-              iL = bf.output(label_out, (size_t)R), iM = bf.output(vertex_score ? max_score_out : nullptr, (size_t)R * 4),
-              iSt = bf.scratch(sizeof(ListState));
+              iN = bf.output(n_vertices_out, (size_t)R * 4, 0), iA = bf.output(area_out, (size_t)R * 8, 0),
+              iIa = bf.output(iface_area_out, (size_t)R * 8, 0), iL = bf.output(label_out, (size_t)R),
+              iM = bf.output(vertex_score ? max_score_out : nullptr, (size_t)R * 4, 0),           // (a NULL output is not cleared)
+              iSt = bf.scratch(sizeof(ListState), 0);
     ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iSt), 0, sizeof(ListState), bf.stm), "surface_residues");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iN), 0, (size_t)R * 4, bf.stm), "surface_residues");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iA), 0, (size_t)R * 8, bf.stm), "surface_residues");
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iIa), 0, (size_t)R * 8, bf.stm), "surface_residues");
-    if (rc == 0 && vertex_score) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iM), 0, (size_t)R * 4, bf.stm), "surface_residues");
     if (rc == 0) {
-        hipLaunchKernelGGL(k_surf_residue_acc, dim3(blocks_of(V)), dim3(SF_NT), 0, bf.stm, V, (int)n_struct, bf.ptr<const int>(iVo), bf.ptr<const int>(iAo),
+        hipLaunchKernelGGL(k_surf_residue_acc, dim3(blocks((size_t)V, SF_NT)), dim3(SF_NT), 0, bf.stm, V, (int)n_struct, bf.ptr<const int>(iVo), bf.ptr<const int>(iAo),
                            bf.ptr<const int>(iRo), bf.ptr<const int>(iNe), bf.ptr<const int>(iAr), bf.ptr<const long long>(iAf),
                            bf.ptr<const unsigned char>(iIf), bf.ptr<const float>(iSc), bf.ptr<int>(iN), bf.ptr<long long>(iA), bf.ptr<long long>(iIa),
                            bf.ptr<unsigned>(iM), bf.ptr<ListState>(iSt));
-        hipLaunchKernelGGL(k_surf_residue_fin, dim3(blocks_of(R)), dim3(SF_NT), 0, bf.stm, R, bf.ptr<const long long>(iA), bf.ptr<const long long>(iIa),
+        hipLaunchKernelGGL(k_surf_residue_fin, dim3(blocks((size_t)R, SF_NT)), dim3(SF_NT), 0, bf.stm, R, bf.ptr<const long long>(iA), bf.ptr<const long long>(iIa),
                            bf.ptr<unsigned char>(iL), bf.ptr<unsigned>(iM));
         rc = bf.read(iSt, &hs, sizeof hs);
     }
@@ -365,12 +356,11 @@ int pesto_surface_vertex_scores(pesto_model* m, int64_t n_vertices, int64_t n_at
     if (int rc = begin(m, ptr_kind)) return rc;
     Buffers bf(ptr_kind, stream);
     const int iNe = bf.input(nearest, (size_t)n_vertices * 4), iP = bf.input(p_atom, (size_t)n_atoms * 4), iO = bf.output(out, (size_t)n_vertices * 4),
-              iSt = bf.scratch(sizeof(ListState));
+              iSt = bf.scratch(sizeof(ListState), 0);
     ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iSt), 0, sizeof(ListState), bf.stm), "surface_vertex_scores");
     if (rc == 0) {
-        hipLaunchKernelGGL(k_surf_gather, dim3(blocks_of(n_vertices)), dim3(SF_NT), 0, bf.stm, (long long)n_vertices, (long long)n_atoms,
+        hipLaunchKernelGGL(k_surf_gather, dim3(blocks((size_t)n_vertices, SF_NT)), dim3(SF_NT), 0, bf.stm, (long long)n_vertices, (long long)n_atoms,
                            bf.ptr<const int>(iNe), bf.ptr<const float>(iP), bf.ptr<float>(iO), bf.ptr<ListState>(iSt));
         rc = bf.read(iSt, &hs, sizeof hs);
     }
@@ -391,33 +381,22 @@ int pesto_surface_scored(pesto_model* m, int32_t n_struct, const int32_t* r_offs
     const int iRo = bf.table(r_offsets, ((size_t)n_struct + 1) * 4), iN = bf.input(n_vertices, (size_t)R * 4), iL = bf.input(label, (size_t)R),
               iP = bf.input(p_res, (size_t)R * 4), iVa = bf.input(valid, (size_t)R), iO = bf.output(offsets_out, ((size_t)n_struct + 1) * 8),
               iRes = bf.partial(residue_out, cap * 4), iY = bf.partial(y_out, cap), iPo = bf.partial(p_out, cap * 4),
-              iCnt = bf.scratch((size_t)n_struct * 4), iSt = bf.scratch(sizeof(ListState));
+              iCnt = bf.scratch((size_t)n_struct * 4), iSt = bf.scratch(sizeof(ListState), 0);
     ListState hs = {};
     int rc = bf.upload();
-    if (rc == 0) rc = hip_ok(hipMemsetAsync(bf.ptr<void>(iSt), 0, sizeof(ListState), bf.stm), "surface_scored");
     if (rc == 0) {
         const dim3 grid((unsigned)n_struct);
         hipLaunchKernelGGL(k_surf_scored<false>, grid, dim3(SF_NT), 0, bf.stm, bf.ptr<const int>(iRo), bf.ptr<const int>(iN),
                            bf.ptr<const unsigned char>(iL), bf.ptr<const float>(iP), bf.ptr<const unsigned char>(iVa), bf.ptr<int>(iCnt),
                            (const long long*)nullptr, (const ListState*)bf.ptr<ListState>(iSt), (int*)nullptr, (unsigned char*)nullptr, (float*)nullptr);
-        hipLaunchKernelGGL(k_list_offsets, dim3(1), dim3(LIST_SCAN_NT), 0, bf.stm, (int)n_struct, bf.ptr<const int>(iCnt), bf.ptr<long long>(iO),
-                           (long long)capacity, bf.ptr<ListState>(iSt));
+        list_offsets(bf, (int)n_struct, iCnt, iO, (long long)capacity, iSt);
         hipLaunchKernelGGL(k_surf_scored<true>, grid, dim3(SF_NT), 0, bf.stm, bf.ptr<const int>(iRo), bf.ptr<const int>(iN),
                            bf.ptr<const unsigned char>(iL), bf.ptr<const float>(iP), bf.ptr<const unsigned char>(iVa), bf.ptr<int>(iCnt),
                            bf.ptr<const long long>(iO), (const ListState*)bf.ptr<ListState>(iSt), bf.ptr<int>(iRes), bf.ptr<unsigned char>(iY),
                            bf.ptr<float>(iPo));
-        rc = hip_ok(hipGetLastError(), "surface_scored: launch failed");
     }
     // the one synchronisation for sizing: the count
-    if (rc == 0) rc = bf.read(iSt, &hs, sizeof hs);
-    if (rc == 0) rc = hip_ok(hipStreamSynchronize(bf.stm), "surface_scored: stream synchronisation failed");
-    if (rc == 0) {
-        sizes_out[0] = hs.K;
-        if (hs.fits) {
-            rc = bf.fetch(iRes, (size_t)hs.K * 4);
-            if (rc == 0) rc = bf.fetch(iY, (size_t)hs.K);
-            if (rc == 0) rc = bf.fetch(iPo, (size_t)hs.K * 4);
-        }
-    }
+    if (rc == 0) rc = bf.verdict(iSt, &hs, sizeof hs, "surface_scored");
+    if (rc == 0) rc = list_tail(bf, hs, sizes_out, {{iRes, 4}, {iY, 1}, {iPo, 4}});
     return bf.finish(rc, "surface_scored");
 }

@@ -371,15 +371,15 @@ int pesto_contact_counts(pesto_model* m, int64_t F, int64_t Na, int64_t Nb, cons
     Buffers bf(ptr_kind, stream);
     const size_t n_out = (size_t)(Na * Nb) * B;
     const int iA = bf.input(xyz_a, (size_t)F * Na * 12), iB = xyz_b == xyz_a ? iA : bf.input(xyz_b, (size_t)F * Nb * 12);
-    const int iS = bf.table(sq.data(), sq.size() * 4), iC = bf.output(counts_out, n_out * 4), iP = bf.output(P_out, n_out * 4);
+    const int iS = bf.table(sq.data(), sq.size() * 4), iC = bf.output(counts_out, n_out * 4, splits > 1 ? 0 : -1),
+              iP = bf.output(P_out, n_out * 4);               // (split frames add their counts up)
     int rc = bf.upload();
     if (rc == 0) {
         const int top = pow2_floor(B);
         const size_t smem = 2 * (size_t)CF * CT * 16 + (size_t)B * NT * 4 + 2 * (size_t)top * 4;
         unsigned* cnt = bf.ptr<unsigned>(iC);
-        hipError_t e = hipFuncSetAttribute((const void*)k_contact_counts, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e == hipSuccess && splits > 1) e = hipMemsetAsync(cnt, 0, n_out * 4, bf.stm);
-        if ((rc = hip_ok(e, "contact_counts")) == 0) {
+        rc = hip_ok(hipFuncSetAttribute((const void*)k_contact_counts, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), "contact_counts");
+        if (rc == 0) {
             hipLaunchKernelGGL(k_contact_counts, dim3((unsigned)(tiles * splits)), dim3(NT), smem, bf.stm, (int)F, (int)Na, (int)Nb,
                                bf.ptr<const float>(iA), bf.ptr<const float>(iB), B, top, bf.ptr<const float>(iS), cnt, (int)tiles_j, (int)tiles, (int)splits,
                                (int)per_split);
