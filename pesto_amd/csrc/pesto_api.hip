@@ -1028,34 +1028,30 @@ int pesto_knn_collate(pesto_model* m, int64_t n_total, int32_t n_struct, const i
         if (struct_offsets[s + 1] <= struct_offsets[s]) return fail(PESTO_ERR_INVALID, "empty or unordered structure %d", s);
     HIP_TRY(hipSetDevice(m->device));
     const size_t id_sz = ids_kind == PESTO_IDS_INT64 ? 8 : 4;
-    // structures of at least knn_cell_min() atoms go through a cell grid (O(N) instead of O(N^2)); each owns one block ("slot") of
-    // the cell arrays. The slot table travels behind the offsets in the same device buffer.
-    std::vector<int> host_tab((size_t)2 * n_struct + 1);
-    int n_slots = 0;
-    const bool brute = m->knn_brute;
-    for (int s = 0; s <= n_struct; ++s) host_tab[s] = struct_offsets[s];
-    for (int s = 0; s < n_struct; ++s)
-        host_tab[n_struct + 1 + s] = (!brute && struct_offsets[s + 1] - struct_offsets[s] >= knn_cell_min()) ? n_slots++ : -1;
-    const int use_grid = n_slots > 0;
-    if (m->knn_off.ensure(host_tab.size() * 4)) return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
+    // a batch with a structure of at least knn_cell_min() atoms gets the cell grids of pesto_cellgrid.h (O(N) instead of O(N^2) for the
+    // large members), sized from the atom count alone: at the n_total limit checked above the cell arrays hold 2 n_total + 65 n_struct
+    // <= 67 * 22.4e6 = 1.5e9 ints, which an int index still spans
+    bool use_grid = false;
+    for (int s = 0; s < n_struct && !m->knn_brute; ++s) use_grid = use_grid || struct_offsets[s + 1] - struct_offsets[s] >= knn_cell_min();
+    const size_t off_bytes = ((size_t)n_struct + 1) * 4;
+    if (m->knn_off.ensure(off_bytes)) return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
     m->knn_off_host.clear();      // (the device copy is about to change: valid again only once the upload below has been queued - ADVICE r5)
     if (use_grid) {
-        const size_t cells = (size_t)n_slots * knn_cells_per_struct();
-        if (m->knn_grids.ensure((size_t)n_struct * knn_grid_struct_bytes()) || m->knn_cnt.ensure(cells * 4) || m->knn_cur.ensure(cells * 4) ||
+        const KnnGridBytes gb = knn_grid_bytes((size_t)n_total, (size_t)n_struct);
+        if (m->knn_grids.ensure(gb.grids) || m->knn_cnt.ensure(gb.cells) || m->knn_cur.ensure(gb.cells) ||
             m->knn_cell.ensure((size_t)n_total * 4) || m->knn_sorted.ensure((size_t)n_total * 16))
             return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
     }
     auto knn_launch = [&](hipStream_t s_, const float* Xd, void* out) {
-        launch_knn_collate(s_, (int)n_total, n_struct, m->knn_off.as<int>(), Xd, k, out, ids_kind, use_grid, m->knn_off.as<int>() + n_struct + 1,
-                           m->knn_grids.p, m->knn_cnt.as<int>(),
-                           m->knn_cur.as<int>(), m->knn_cell.as<int>(), m->knn_sorted.p);
+        launch_knn_collate(s_, (int)n_total, n_struct, m->knn_off.as<int>(), Xd, k, out, ids_kind, use_grid ? m->knn_grids.p : nullptr,
+                           m->knn_cnt.as<int>(), m->knn_cur.as<int>(), m->knn_cell.as<int>(), m->knn_sorted.p);
     };
     if (ptr_kind == PESTO_PTR_DEVICE) {
         hipStream_t st = (hipStream_t)stream;
         Sequence seq(m, st);
         if (seq.rc) return seq.rc;
-        HIP_TRY(hipMemcpyAsync(m->knn_off.p, host_tab.data(), host_tab.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));     // host_tab is a local: finish the copy before returning
+        HIP_TRY(hipMemcpyAsync(m->knn_off.p, struct_offsets, off_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));     // struct_offsets is the caller's: finish the copy before returning
         m->knn_off_host.assign(struct_offsets, struct_offsets + n_struct + 1);      // (what the device holds now)
         knn_launch(st, X, ids_out);
         HIP_TRY(hipGetLastError());
@@ -1066,7 +1062,7 @@ int pesto_knn_collate(pesto_model* m, int64_t n_total, int32_t n_struct, const i
     if (m->in_X.ensure((size_t)n_total * 12) || m->in_ids.ensure((size_t)n_total * KMAX * id_sz)) return fail(PESTO_ERR_NOMEM, "staging allocation failed");
     Sequence seq(m, st);
     if (seq.rc) return seq.rc;
-    HIP_TRY(hipMemcpyAsync(m->knn_off.p, host_tab.data(), host_tab.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->knn_off.p, struct_offsets, off_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(m->in_X.p, X, (size_t)n_total * 12, hipMemcpyHostToDevice, st));
     knn_launch(st, m->in_X.as<float>(), m->in_ids.p);
     HIP_TRY(hipGetLastError());
@@ -1089,8 +1085,8 @@ int pesto_knn_tie_rows(pesto_model* m, int64_t n_total, int32_t n_struct, const 
         if (struct_offsets[s + 1] <= struct_offsets[s]) return fail(PESTO_ERR_INVALID, "empty or unordered structure %d", s);
     HIP_TRY(hipSetDevice(m->device));
     const size_t id_sz = ids_kind == PESTO_IDS_INT64 ? 8 : 4;
-    if (m->knn_off.cap < ((size_t)2 * n_struct + 1) * 4) m->knn_off_host.clear();      // (a reallocation drops the device copy)
-    if (m->knn_off.ensure(((size_t)2 * n_struct + 1) * 4)) return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
+    if (m->knn_off.cap < ((size_t)n_struct + 1) * 4) m->knn_off_host.clear();      // (a reallocation drops the device copy)
+    if (m->knn_off.ensure(((size_t)n_struct + 1) * 4)) return fail(PESTO_ERR_NOMEM, "workspace allocation failed");
     hipStream_t st = ptr_kind == PESTO_PTR_DEVICE ? (hipStream_t)stream : (stream ? (hipStream_t)stream : m->stream);
     Sequence seq(m, st);
     if (seq.rc) return seq.rc;

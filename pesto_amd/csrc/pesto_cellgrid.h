@@ -1,19 +1,21 @@
-// pesto_cellgrid.h - the float32 uniform cell grid of the contact searches (interface labels, pesto_eval.hip; dataset contacts,
-// pesto_contacts.hip) and torch.norm's distance; pesto_lddt.hip builds its reference list on the same grid. The scans: pesto_scan.h.
+// pesto_cellgrid.h - the float32 uniform cell grid of the project's neighbour searches: the contact searches (interface labels,
+// pesto_eval.hip; dataset contacts, pesto_contacts.hip), lDDT's reference list (pesto_lddt.hip) and the k-NN topology (pesto_knn.hip);
+// and torch.norm's distance. The scans: pesto_scan.h.
 //
-// Both searches replace the reference's dense torch distance matrix per pair of subunits (locate_contacts / extract_all_contacts,
+// The contact searches replace the reference's dense torch distance matrix per pair of subunits (locate_contacts / extract_all_contacts,
 // src/data_encoding.py:116-176): every atom pair of two subunits of one assembly with |x_a - x_b| < r_thr, the distance being the
 // reference's fp32 torch.norm (dist()). Each assembly of the batch gets a grid of its own:
 //   - cells at least r_thr * 1.001 wide, so a pair within r_thr is never more than one cell apart, whatever the rounding of the cell
 //     coordinates: the searching atom walks the 3 x 3 rows of three consecutive cells around it (for_each_neighbour) and misses nobody.
-//     Whoever changes the cell edge, cell3() or the walk changes this argument for BOTH searches;
+//     Whoever changes the cell edge, cell3() or the walk changes this argument for the contact searches AND lDDT, and the completeness
+//     radius of the k-NN (k_knn_collate walks blocks of cells of its own on top of cell3() and derives the edge from inv_h);
 //   - at most 64 cells per axis and 2 N_s + 64 cells in all (the edge grows by h *= 1.25f until they fit), so the cell arrays of a batch
 //     are sized from the atom count alone: assembly s owns the cells from cells_before(off_s, s), one more than it uses (the total behind
 //     its last cell), and a batch needs cells_before(n_total, n_struct);
-//   - one cell (every pair is examined) when the bounding box is not finite: an atom with a NaN coordinate is farther than r_thr from
-//     everybody, itself included, in every comparison.
-// Build: k_grid_setup -> k_grid_count -> k_grid_scan -> k_grid_scatter, four launches; the users differ in what they check per atom in
-// the count pass and in the payload they scatter beside the coordinates, both functors.
+//   - one cell (every pair is examined, inv_h = 0) when the bounding box is not finite: an atom with a NaN coordinate is farther than
+//     r_thr from everybody, itself included, in every comparison.
+// Build: grid_build() = k_grid_setup -> k_grid_count -> k_grid_scan -> k_grid_scatter, four launches over the five buffers of GridBufs;
+// the users differ in what they check per atom in the count pass and in the payload they scatter beside the coordinates, both functors.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,12 +39,17 @@ __device__ __forceinline__ void cell3(const CellGrid& g, float x, float y, float
     cz = min(g.nz - 1, max(0, (int)((z - g.minz) * g.inv_h)));
 }
 
-// torch.norm's float32 distance: sqrt(fma(z, z, fma(y, y, x * x))), every step rounded as written (the build contracts only within a
-// source expression, so the chain is spelled out rather than left to the compiler); the same chain as knn_key's
-__device__ __forceinline__ float dist(float4 a, float4 b) {
-    const float rx = b.x - a.x, ry = b.y - a.y, rz = b.z - a.z;
+// torch.norm's float32 length of a difference vector: sqrt(fma(z, z, fma(y, y, x * x))), every step rounded as written (the build
+// contracts only within a source expression, so the chain is spelled out rather than left to the compiler). The one chain of the contact
+// searches (dist) and of the k-NN's keys (knn_key)
+__device__ __forceinline__ float norm3(float rx, float ry, float rz) {
     return sqrtf(__fmaf_rn(rz, rz, __fmaf_rn(ry, ry, __fmul_rn(rx, rx))));
 }
+__device__ __forceinline__ float dist(float4 a, float4 b) { return norm3(b.x - a.x, b.y - a.y, b.z - a.z); }
+
+// for the users that check nothing in the count pass / keep nothing beside the coordinates
+struct NoCheck { __device__ void operator()(int, int) const {} };
+struct NoPayload { __device__ void operator()(int, int) const {} };
 
 // one workgroup per assembly: bounding box -> cell size and counts, cleared cell counters
 __global__ __launch_bounds__(256) void k_grid_setup(int n_struct, const int* __restrict__ offsets, const float* __restrict__ X, float r_thr,
@@ -127,6 +134,23 @@ __global__ __launch_bounds__(256) void k_grid_scatter(int n_total, int n_struct,
     const int pos = offsets[s] + atomicAdd(&cell_cur[grids[s].base + cell_of[i]], 1);
     sorted[pos] = make_float4(X[3 * (size_t)i], X[3 * (size_t)i + 1], X[3 * (size_t)i + 2], __int_as_float(i));
     payload(pos, i);
+}
+
+// the five device buffers of a batch's grids: grids [n_struct], cell_cnt / cell_cur [cells_before(n_total, n_struct)] (cell_cnt ends up as
+// the cell starts), cell_of [n_total], sorted [n_total]
+struct GridBufs { CellGrid* grids; int* cell_cnt; int* cell_cur; int* cell_of; float4* sorted; };
+
+// the build, host side: the grids of every assembly for cells of at least r_thr * 1.001, the atoms in cell order in b.sorted
+template <class Check, class Payload>
+void grid_build(hipStream_t st, int n_total, int n_struct, const int* offsets, const float* X, float r_thr, const GridBufs& b, Check check,
+                Payload payload) {
+    const dim3 atoms((n_total + 255) / 256), structs(n_struct);
+    const CellGrid* g = b.grids;
+    hipLaunchKernelGGL(k_grid_setup, structs, dim3(256), 0, st, n_struct, offsets, X, r_thr, b.grids, b.cell_cnt);
+    hipLaunchKernelGGL(k_grid_count<Check>, atoms, dim3(256), 0, st, n_total, n_struct, offsets, X, g, b.cell_cnt, b.cell_of, check);
+    hipLaunchKernelGGL(k_grid_scan, structs, dim3(1024), 0, st, g, b.cell_cnt, b.cell_cur);
+    hipLaunchKernelGGL(k_grid_scatter<Payload>, atoms, dim3(256), 0, st, n_total, n_struct, offsets, X, g, (const int*)b.cell_of, b.cell_cur,
+                       b.sorted, payload);
 }
 
 // visit(j) for every sorted position j of the 3 x 3 rows of three consecutive cells around atom a of the assembly whose atoms start at

@@ -231,12 +231,8 @@ void launch_contacts(hipStream_t s, int n_total, int n_struct, int n_sub, const 
                      int n_types, float r_thr, int cap_pairs, int cap_groups, const CtBuffers& w, int* pairs_out, float* d_out, int* groups_out,
                      unsigned short* keys_out, unsigned short* rkeys_out, unsigned char* T_out, unsigned char* ties_out) {
     const int nb = (n_total + 255) / 256, nbk = (cap_pairs + 255) / 256;
-    hipLaunchKernelGGL(k_grid_setup, dim3(n_struct), dim3(256), 0, s, n_struct, (const int*)w.offsets, X, r_thr, w.grids, w.cell_cnt);
-    hipLaunchKernelGGL(k_grid_count<CtCheck>, dim3(nb), dim3(256), 0, s, n_total, n_struct, (const int*)w.offsets, X, (const CellGrid*)w.grids,
-                       w.cell_cnt, w.cell_of, CtCheck{w.offsets, subunit, residue, type, n_sub, n_types, w.st});
-    hipLaunchKernelGGL(k_grid_scan, dim3(n_struct), dim3(1024), 0, s, (const CellGrid*)w.grids, w.cell_cnt, w.cell_cur);
-    hipLaunchKernelGGL(k_grid_scatter<CtPayload>, dim3(nb), dim3(256), 0, s, n_total, n_struct, (const int*)w.offsets, X, (const CellGrid*)w.grids,
-                       (const int*)w.cell_of, w.cell_cur, w.sorted, CtPayload{subunit, w.sorted_sub});
+    grid_build(s, n_total, n_struct, (const int*)w.offsets, X, r_thr, GridBufs{w.grids, w.cell_cnt, w.cell_cur, w.cell_of, w.sorted},
+               CtCheck{w.offsets, subunit, residue, type, n_sub, n_types, w.st}, CtPayload{subunit, w.sorted_sub});
     // count -> per-atom ranges -> emit in (a, b) order
     hipLaunchKernelGGL(k_ct_pairs<false>, dim3(nb), dim3(256), 0, s, n_total, n_struct, (const int*)w.offsets, (const CellGrid*)w.grids,
                        (const int*)w.cell_cnt, (const float4*)w.sorted, (const int*)w.sorted_sub, r_thr, w.off, ties_out, (const int*)nullptr,

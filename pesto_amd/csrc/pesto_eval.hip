@@ -15,7 +15,6 @@ namespace {
 // replaces: locate_contacts / extract_all_contacts (src/data_encoding.py:116-176), contacts_types (processing/build_dataset.py:38-51) and
 // load_interface_labels (data_handler.py:9-23) OR-ed over the partners of a subunit (data_handler.py:100-126):
 //     labels[res(a)] |= partner_mask[b]   for every receptor atom a and atom b of another subunit of the same assembly with |x_a - x_b| < r_thr
-struct LblNoCheck { __device__ void operator()(int, int) const {} };
 // beside the sorted coordinates: (subunit, partner mask)
 struct LblPayload {
     const int* subunit; const unsigned* pmask; int2* sorted_sm;
@@ -149,16 +148,10 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_scores(int n_class, const int
 
 void launch_contact_labels(hipStream_t st, int n_total, int n_struct, const int* offsets, const float* X, const int* subunit, const int* residue,
                            const unsigned char* receptor, const unsigned* pmask, int n_res, float r_thr, unsigned* labels, unsigned char* ties,
-                           CellGrid* g, int* cell_cnt, int* cell_cur, int* cell_of, float4* sorted, int2* sorted_sm, int* err) {
-    const int nb = (n_total + 255) / 256;
-    hipLaunchKernelGGL(k_grid_setup, dim3(n_struct), dim3(256), 0, st, n_struct, offsets, X, r_thr, g, cell_cnt);
-    hipLaunchKernelGGL(k_grid_count<LblNoCheck>, dim3(nb), dim3(256), 0, st, n_total, n_struct, offsets, X, (const CellGrid*)g, cell_cnt, cell_of,
-                       LblNoCheck{});
-    hipLaunchKernelGGL(k_grid_scan, dim3(n_struct), dim3(1024), 0, st, (const CellGrid*)g, cell_cnt, cell_cur);
-    hipLaunchKernelGGL(k_grid_scatter<LblPayload>, dim3(nb), dim3(256), 0, st, n_total, n_struct, offsets, X, (const CellGrid*)g,
-                       (const int*)cell_of, cell_cur, sorted, LblPayload{subunit, pmask, sorted_sm});
-    hipLaunchKernelGGL(k_contact_labels, dim3(nb), dim3(256), 0, st, n_total, n_struct, offsets, (const CellGrid*)g, (const int*)cell_cnt,
-                       (const float4*)sorted, (const int2*)sorted_sm, residue, receptor, n_res, r_thr, labels, ties, err);
+                           const GridBufs& g, int2* sorted_sm, int* err) {
+    grid_build(st, n_total, n_struct, offsets, X, r_thr, g, NoCheck{}, LblPayload{subunit, pmask, sorted_sm});
+    hipLaunchKernelGGL(k_contact_labels, dim3((n_total + 255) / 256), dim3(256), 0, st, n_total, n_struct, offsets, (const CellGrid*)g.grids,
+                       (const int*)g.cell_cnt, (const float4*)g.sorted, (const int2*)sorted_sm, residue, receptor, n_res, r_thr, labels, ties, err);
 }
 
 void launch_bc_scores(hipStream_t st, int n_struct, int n_class, const int* roff, const unsigned char* y, const float* p, float* out) {
@@ -194,8 +187,9 @@ int pesto_interface_labels(pesto_model* m, int64_t n_total, int32_t n_struct, co
     if (rc == 0) {
         launch_contact_labels(bf.stm, (int)n_total, n_struct, bf.ptr<const int>(iOff), bf.ptr<const float>(iX), bf.ptr<const int>(iS),
                               bf.ptr<const int>(iR), bf.ptr<const unsigned char>(iT), bf.ptr<const unsigned>(iM), (int)n_res, r_thr,
-                              bf.ptr<unsigned>(iL), bf.ptr<unsigned char>(iTi), bf.ptr<CellGrid>(iG), bf.ptr<int>(iCnt), bf.ptr<int>(iCur),
-                              bf.ptr<int>(iCell), bf.ptr<float4>(iSort), bf.ptr<int2>(iSm), bf.ptr<int>(iErr));
+                              bf.ptr<unsigned>(iL), bf.ptr<unsigned char>(iTi),
+                              GridBufs{bf.ptr<CellGrid>(iG), bf.ptr<int>(iCnt), bf.ptr<int>(iCur), bf.ptr<int>(iCell), bf.ptr<float4>(iSort)},
+                              bf.ptr<int2>(iSm), bf.ptr<int>(iErr));
         rc = bf.read(iErr, &err, 4);
     }
     rc = bf.finish(rc, "interface_labels");

@@ -1,4 +1,4 @@
-// pesto_kernels.h - launchers of the gfx950 kernels (definitions in pesto_kernels.hip / pesto_node.hip / pesto_edge.hip)
+// pesto_kernels.h - launchers of the gfx950 kernels (definitions in pesto_kernels.hip / pesto_knn.hip / pesto_node.hip / pesto_edge.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,18 +64,18 @@ void launch_edge(hipStream_t st, const float* W, const LayerW& lw, int N1, const
 // state there - p_state / q_state (the old state, still gathered by other workgroups) must be different buffers; Z is not used.
 // next non-null: it also writes layer `next`'s records of the new state into rec_nb_out / rec_cen_out (prepare phase; buffers
 // different from rec_nb / rec_cen, which other workgroups still read)
-// k-NN + collate; with use_grid the structures of at least knn_cell_min() atoms are searched through a uniform cell grid
-// (buffers: slots n_struct ints = block of the cell arrays per structure or -1, grids n_struct * knn_grid_struct_bytes(), cell_cnt /
-// cell_cur n_slots * knn_cells_per_struct() ints, cell_of n_total ints, sorted n_total float4), smaller ones by brute force; identical
-// results either way
+// k-NN + collate (pesto_knn.hip). With grids non-null the batch gets the cell grids of pesto_cellgrid.h (grids: knn_grid_bytes().grids
+// bytes; cell_cnt / cell_cur: knn_grid_bytes().cells bytes each; cell_of n_total ints; sorted n_total float4) and the structures of at
+// least knn_cell_min() atoms are searched through them, smaller ones by brute force; grids null (the other four are then unused): brute
+// force for everybody, no grid launches. Identical results either way
 void launch_knn_collate(hipStream_t st, int n_total, int n_struct, const int* offsets, const float* X, int k, void* ids_out, int ids_kind,
-                        int use_grid, const int* slots, void* grids, int* cell_cnt, int* cell_cur, int* cell_of, void* sorted);
+                        void* grids, int* cell_cnt, int* cell_cur, int* cell_of, void* sorted);
 // flags[i] bit c set: an exact distance tie of row i straddles the cut after column 8 << c of the table `ids` ([n_total, 64], 1-based)
 void launch_knn_ties(hipStream_t st, int n_total, int n_struct, const int* offsets, const float* X, int k, const void* ids, int ids_kind,
                      unsigned char* flags);
-size_t knn_grid_struct_bytes();
+struct KnnGridBytes { size_t grids, cells; };
+KnnGridBytes knn_grid_bytes(size_t n_total, size_t n_struct);
 int knn_cell_min();
-int knn_cells_per_struct();
 // meta: device array of {int off, roff, n, r, k; long long idoff} per structure (32 bytes each, see k_collate)
 // seg_of_atom [n_total] / seg_end [n_struct]: structure index of every atom and the end offset of every structure (for launch_unpack)
 void launch_collate(hipStream_t st, int n_total, int n_struct, const void* meta, const void* ids_raw, int ids_kind, const int* roa_raw,

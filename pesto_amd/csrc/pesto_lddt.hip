@@ -76,7 +76,6 @@ __global__ __launch_bounds__(NT) void k_lddt_check(int N, int R, int n_struct, l
 }
 
 // ------------------------------------------------------------------------------------------------ the reference list
-struct NoCheck { __device__ void operator()(int, int) const {} };
 // beside the sorted coordinates: (residue row, or -1 for an atom outside the selection or without finite coordinates; chain)
 struct MetaPayload {
     const int* res; const int* chain; const unsigned char* sel; int2* meta;
@@ -85,7 +84,7 @@ struct MetaPayload {
 
 // The grid is built on a copy of the reference in which every atom with a non-finite coordinate is marked as outside the selection
 // and sits on the first finite atom of its structure (the origin for a structure without one): such an atom has no pairs by the
-// definition, and the grid's bounding box (k_grid_setup) then only ever sees finite coordinates and is no larger than the finite atoms'
+// definition, and the grid's bounding box (grid_build's set-up) then only ever sees finite coordinates and is no larger than the finite atoms'
 // own. k_lddt_anchor, one workgroup per structure: anchor[s] = the first atom with three finite coordinates, or -1.
 __device__ __forceinline__ bool finite3(const float* __restrict__ Y, int i) {
     return isfinite(Y[3 * (size_t)i]) && isfinite(Y[3 * (size_t)i + 1]) && isfinite(Y[3 * (size_t)i + 2]);
@@ -326,13 +325,8 @@ int list_count(Buffers& bf, const ListScratch& ls, int N, int n_struct, const in
     hipLaunchKernelGGL(k_lddt_clean, dim3(nb), dim3(NT), 0, bf.stm, N, n_struct, offs, (const int*)bf.ptr<int>(ls.iAnchor), ref, res, sel, clean, keep,
                        bf.ptr<ListState>(iSt));
     ref = clean;
-    hipLaunchKernelGGL(k_grid_setup, dim3(n_struct), dim3(256), 0, bf.stm, n_struct, offs, ref, r_incl / scale, g, cell_cnt);
-    hipLaunchKernelGGL(k_grid_count<NoCheck>, dim3(nb), dim3(256), 0, bf.stm, N, n_struct, offs, ref, (const CellGrid*)g, cell_cnt,
-                       bf.ptr<int>(ls.iCell), NoCheck{});
-    hipLaunchKernelGGL(k_grid_scan, dim3(n_struct), dim3(1024), 0, bf.stm, (const CellGrid*)g, cell_cnt, bf.ptr<int>(ls.iCur));
-    hipLaunchKernelGGL(k_grid_scatter<MetaPayload>, dim3(nb), dim3(256), 0, bf.stm, N, n_struct, offs, ref, (const CellGrid*)g,
-                       (const int*)bf.ptr<int>(ls.iCell), bf.ptr<int>(ls.iCur), bf.ptr<float4>(ls.iSort),
-                       MetaPayload{res, chain, keep, bf.ptr<int2>(ls.iMeta)});
+    grid_build(bf.stm, N, n_struct, offs, ref, r_incl / scale, GridBufs{g, cell_cnt, bf.ptr<int>(ls.iCur), bf.ptr<int>(ls.iCell), bf.ptr<float4>(ls.iSort)},
+               NoCheck{}, MetaPayload{res, chain, keep, bf.ptr<int2>(ls.iMeta)});
     hipLaunchKernelGGL(k_lddt_list<false>, dim3(nb), dim3(NT), 0, bf.stm, N, n_struct, offs, (const CellGrid*)g, (const int*)cell_cnt,
                        (const float4*)bf.ptr<float4>(ls.iSort), (const int2*)bf.ptr<int2>(ls.iMeta), mode, s_star, scale, bf.ptr<int>(ls.iRow),
                        (const long long*)nullptr, (int*)nullptr, (float*)nullptr);

@@ -13,8 +13,11 @@ from pesto_amd.weights import synthetic_state_dict
 
 m = Model(CONFIGS["i_v4_0"]).to("cuda:0")
 m.load_state_dict(synthetic_state_dict(CONFIGS["i_v4_0"]))
-for name, sizes in (("8 x N=3000 (bench batch)", [3000] * 8), ("1 x N=20000 (config 5)", [20000]), ("53 chains, N 1641-3052", list(np.random.default_rng(0).integers(1641, 3053, 53)))):
+for name, sizes in (("8 x N=3000 (bench batch)", [3000] * 8), ("1 x N=20000 (config 5)", [20000]), ("53 chains, N 1641-3052", list(np.random.default_rng(0).integers(1641, 3053, 53))),
+                    ("sparse cube 250 A, N=20000", [20000])):
     Xs = [synthetic_cloud(int(n), 7 + i) for i, n in enumerate(sizes)]
+    if name.startswith("sparse"):       # uniform over a 250 A cube: the cell cap of pesto_cellgrid.h binds, most cells are empty
+        Xs = [np.random.default_rng(5).uniform(0, 250, (sizes[0], 3)).astype(np.float32)]
     X = np.concatenate(Xs)
     Xd = torch.from_numpy(X).cuda()
     for _ in range(3):

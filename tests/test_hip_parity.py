@@ -2,6 +2,8 @@
 reference PyTorch CPU path and (b) the CPU oracle on the same seeded inputs.
 Tolerances: whole forward 1e-4 abs on z (the north-star's fp32 bound; measured 1-3e-5); per stage 1e-5 abs for the
 small stages and 1e-6 of the state scale for a layer (see stage_tol)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -611,6 +613,91 @@ def test_knn_cell_grid_vs_host_contract_and_forward():
     z = m.forward_segments(X, ids, q, roa, M.shape[1])
     zo = _oracle("i_v4_0").forward_segments(X, ids.astype(np.int32), q, roa, M.shape[1])
     assert np.abs(z - zo).max() < 1e-4
+
+
+def _knn_edge_cloud(name):
+    """(X, sizes) at the edges of the shared cell grid (pesto_cellgrid.h). The seeds were chosen on the host so that in no structure of
+    more than 64 atoms an exact key tie decides a column of extract_topology's table (checked by sorting once with ties broken by the
+    smallest and once by the largest index), except in the two clouds of coincident atoms, where every tie is between keys that both
+    sides order by index."""
+    from pesto_amd.topology import synthetic_cloud
+    rng = np.random.default_rng(300)
+    if name in ("n1023", "n1024", "n1025"):                  # the threshold between brute force and the grid
+        n = int(name[1:])
+        return synthetic_cloud(n, {1023: 301, 1024: 300, 1025: 302}[n]), [n]
+    if name == "batch":                                      # small members between large ones: g.base, sorted.w - s0
+        sizes = [1500, 40, 1024, 7, 3000]
+        return np.concatenate([synthetic_cloud(n, 300) for n in sizes]), sizes
+    if name == "sparse_cube":                                # the cell cap: the edge grows by 1.25, most cells empty, the blocks must grow
+        return rng.uniform(0, 250, (1024, 3)).astype(np.float32), [1024]
+    if name == "line":                                       # more than 64 cells of 4.5 A along x: ext / 64 governs the edge
+        X = rng.uniform(0, 0.05, (2000, 3)).astype(np.float32)
+        X[:, 0] += (np.arange(2000) * 0.2).astype(np.float32)
+        return X, [2000]
+    if name == "coincident":                                 # masked keys among the first 64 of 1,050 rows: the blocks grow to the whole grid
+        X = synthetic_cloud(1100, 320)
+        X[50:] = X[50]
+        return X, [1100]
+    if name == "point":                                      # ... and a zero-extent box: one cell, every key masked
+        return np.full((1100, 3), 3.25, np.float32), [1100]
+    if name == "flat_x":                                     # one cell layer
+        X = synthetic_cloud(1200, 300)
+        X[:, 0] = np.float32(7.5)
+        return X, [1200]
+    assert name == "cloud2000"
+    return synthetic_cloud(2000, 300), [2000]
+
+
+@functools.lru_cache(maxsize=None)
+def _knn_edge_reference(name):
+    """X, sizes and the table of the host contract (extract_topology per structure, 1-based batch-global ids), computed once"""
+    from pesto_amd.topology import extract_topology
+    X, sizes = _knn_edge_cloud(name)
+    ref = np.zeros((X.shape[0], 64), np.int64)
+    off = 0
+    for n in sizes:
+        ref[off:off + n, :min(n, 64)] = extract_topology(X[off:off + n], 64) + off + 1
+        off += n
+    return X, sizes, ref
+
+
+def _check_knn_edge(m, name, k=64):
+    X, sizes, ref = _knn_edge_reference(name)
+    grid = m.debug_select(0, knn_brute_force=False).knn_collate(X, sizes, k)
+    brute = m.debug_select(0, knn_brute_force=True).knn_collate(X, sizes, k)
+    m.debug_select(0, knn_brute_force=False)
+    assert np.array_equal(grid, brute)
+    assert not grid[:, k:].any()
+    ref = ref[:, :k]
+    off = 0
+    for n in sizes:
+        got, want = grid[off:off + n, :k], ref[off:off + n]
+        _check_same_neighbours(got, want, X[off:off + n], offset=off)
+        if n > 64:          # (a smaller structure lists the atom itself, whose key ties with the farthest atom's by the reference's rule)
+            assert np.array_equal(got, want)
+        off += n
+    return grid
+
+
+@pytest.mark.parametrize("name", ["n1023", "n1024", "n1025", "batch", "sparse_cube", "line", "coincident", "point", "flat_x"])
+def test_knn_shared_cell_grid_edges(name):
+    """The k-NN on the cell grid it shares with the contact searches: at every edge of that grid the table is the brute-force one bit for
+    bit and the host contract's (extract_topology), which does not know the kernel."""
+    _check_knn_edge(_model("i_v4_0"), name)
+
+
+@pytest.mark.parametrize("k", [16, 1])
+def test_knn_shared_cell_grid_fewer_columns(k):
+    _check_knn_edge(_model("i_v4_0"), "cloud2000", k)
+
+
+def test_knn_shared_cell_grid_device_input_equals_host_input():
+    import torch
+    m = _model("i_v4_0")
+    X, sizes, _ = _knn_edge_reference("batch")
+    ids = _check_knn_edge(m, "batch")
+    ids_dev = m.to("cuda:0").knn_collate(torch.from_numpy(X).cuda(), sizes)
+    assert ids_dev.is_cuda and torch.equal(ids_dev.cpu(), torch.from_numpy(ids))
 
 
 def test_bulk_apply_model_pdb_in_pdb_out(tmp_path):
