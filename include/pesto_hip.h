@@ -836,6 +836,47 @@ int pesto_lddt(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int
                int64_t K_in, const int64_t* offsets_in, const int32_t* j_in, const float* d_in, float* score_out,
                float* residue_out, int32_t* preserved_out, int32_t* total_out, int64_t* n_pairs_out, int32_t ptr_kind, void* stream);
 
+/* ---- TM-score and GDT of a model against its reference for a given residue correspondence (Zhang and Skolnick 2004) ----
+ * Failures of the entry point below are reported through pesto_tmscore_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the DockQ group it uses the handle for its device, after
+ * pesto_synchronize(m), allocates its buffers stream-ordered per call, keeps no state between calls and synchronises `stream`.
+ * replaces: what the package lacked next to lDDT and the RMSDs - the global fold measures that the reference's model selection
+ * (interfaceome/selecting_alphafold_models.ipynb) and its MD notebooks' single RMSD curve stand in for; outside the package, one run of
+ * the TMscore program per pair. */
+const char* pesto_tmscore_last_error(void);
+
+enum {
+    PESTO_TMSCORE_MAX_FRAMES = 1 << 23,       /* frames, or structures of a ragged batch, of one call */
+    PESTO_TMSCORE_MAX_LENGTH = 4096,          /* selected atoms of a structure: 64 lanes of a wave times the 64 bits of a lane's word */
+    PESTO_TMSCORE_MAX_ITER = 1024,            /* n_iter */
+    PESTO_TMSCORE_MAX_RAISE = 4096            /* raises of d_cut by 0.5 behind one fit */
+};
+
+/* replaces: the superposition search of the TMscore program for F models of one structure (or one model each of n_struct structures) in
+ * one call. xyz_ref float32 [N,3], xyz float32 [F,N,3] in the same atom order; sel int32 [sel_offsets[n_struct]]: the atoms scored, in
+ * sequence order, structure after structure (sel_offsets int32 [n_struct + 1], host memory, from 0; 3 <= L <= PESTO_TMSCORE_MAX_LENGTH
+ * atoms each; n_struct > 1 needs F = 1). norm_len, d0 double [n_struct], host memory, positive: L_norm and d0 of every structure (the
+ * caller's choice; customarily L and max(0.5, 1.24 cbrt(max(L_norm - 15, 0)) - 1.8)).
+ * Definition, in double from the float32 inputs: d_i = sqrt(|x'_i - y_i|^2) scale under a fit x' = (x - m) R + m_ref (pesto_fit.h, with
+ * its identity short cut); TM(fit) = (sum_i 1 / (1 + (d_i / d0)^2)) / L_norm; count_c(fit) = |{i: d_i < c}|, c = 0.5, 1, 2, 4, 8.
+ * Seeds: the windows of length L >> k (k = 0 .. 5, while above 4), then min(L, 4), at the starts 0, step, 2 step, ... <= L - n and
+ * L - n, numbered length first, then start. A search: S = the window; up to n_iter times: fit on S (the fit is visited), S' = {i: d_i
+ * < d_cut} with d_cut = min(8, max(4.5, d0)) raised by 0.5 while |S'| < 3 (at most PESTO_TMSCORE_MAX_RAISE times, then the seed
+ * ends), stop if S' = S, else S = S'. Per unit u (frame, or structure):
+ *     tm_out float32 [U]: the largest TM over all visited fits; seed_out int32 [U]: the lowest seed that attains it;
+ *     rotation_out double [U,3,3], translation_out double [U,3]: that seed's first such fit as x' = x R + t, t = m_ref - m R
+ *     counts_out int32 [U,5]: the largest count_c over all visited fits; gdt_ts_out = float32(double(c1 + c2 + c4 + c8) / double(4 L)),
+ *     gdt_ha_out likewise over (0.5, 1, 2, 4)
+ *     rmsd_out float32 [U]: pesto_fit_rmsd on sel for fit and measure, bit for bit (its kernel)
+ * A unit with a non-finite selected coordinate (the frame's or the reference's): NaN scores and fit, zero counts, seed -1. sel is
+ * checked on the device before anything dereferences it; a refused call returns PESTO_ERR_INVALID and writes nothing. A wave per seed,
+ * the workgroups of a unit sharing its seeds out, and a second launch for the maximum over the shares: no atomics, and no output depends
+ * on the sharing, so every output is bit-identical from call to call and between a frame alone and in a batch. */
+int pesto_tmscore(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const int32_t* sel_offsets, const int32_t* sel, const float* xyz_ref,
+                  const float* xyz, const double* norm_len, const double* d0, int32_t step, int32_t n_iter, double scale, float* tm_out,
+                  float* gdt_ts_out, float* gdt_ha_out, int32_t* counts_out, float* rmsd_out, int32_t* seed_out, double* rotation_out,
+                  double* translation_out, int32_t ptr_kind, void* stream);
+
 /* ---- essential dynamics of MD frames: fluctuations, covariance, cross-correlation, principal components (Amadei et al. 1993) ----
  * Failures of the entry points below are reported through pesto_dynamics_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the cluster group they use the handle for its device, after

@@ -15,6 +15,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "peaks", "interface_centers", "weighted_centers", "distance_quantile", "density_peaks", "cluster_interface_frames",
            "dockq", "lrmsd", "fit_rmsd", "native_pairs", "capri_class",
            "lddt", "ilddt", "lddt_ca", "reference_pairs", "structure_lddt",
+           "tmscore", "tm_score", "gdt", "tm_ca", "structure_tmscore",
            "dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
@@ -68,6 +69,10 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         ld = importlib.import_module(".lddt", __name__)
         return ld if name == "lddt" else getattr(ld, name)
+    if name in ("tmscore", "tm_score", "gdt", "tm_ca", "structure_tmscore"):
+        import importlib
+        tm = importlib.import_module(".tmscore", __name__)
+        return tm if name == "tmscore" else getattr(tm, name)
     if name in ("dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA"):
         import importlib
         dy = importlib.import_module(".dynamics", __name__)

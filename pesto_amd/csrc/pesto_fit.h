@@ -1,6 +1,6 @@
-// pesto_fit.h - the one superposition fit of the trajectory, docking and DockQ groups (pesto_trajectory.hip, pesto_docking.hip,
-// pesto_dockq.hip): a frame fitted onto a reference on an atom selection (Kabsch; the rotation is kabsch_rotation of pesto_geom.h), a
-// point moved by that fit, the squared deviation summed under it, the RMSD kernel made of the three, and the check of the selections'
+// pesto_fit.h - the one superposition fit of the trajectory, docking, DockQ and TM-score groups (pesto_trajectory.hip, pesto_docking.hip,
+// pesto_dockq.hip, pesto_tmscore.hip): a frame fitted onto a reference on an atom selection (Kabsch; the rotation is kabsch_rotation of
+// pesto_geom.h), by a workgroup or by one wave on a subset of the points, a point moved by that fit, the squared deviation summed under it, the RMSD kernel made of the three, and the check of the selections'
 // indices. The groups promise bit identities between their entry points (pesto_superpose's rmsd_out, pesto_interface_rmsd,
 // pesto_fit_rmsd, pesto_dockq's two RMSDs); they hold because every one of them runs the text below. The library is built with
 // -ffp-contract=on, so an expression here rounds the same way in every kernel that calls it.
@@ -30,6 +30,20 @@ __device__ __forceinline__ auto atoms(const float* __restrict__ X, const int* __
     };
 }
 
+// one point pair's terms of the two mean sums m (and of the count of coordinates that differ), and of the covariance H about the means
+template <bool SHORTCUT>
+__device__ __forceinline__ void mean_terms(const double* x, const double* y, double* m, double& differ) {
+    for (int c = 0; c < 3; ++c) {
+        m[c] += x[c]; m[3 + c] += y[c];
+        if (SHORTCUT) differ += x[c] == y[c] ? 0.0 : 1.0;
+    }
+}
+
+__device__ __forceinline__ void covariance_terms(const double* x, const double* y, const double* m, double* H) {
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) H[3 * a + b] += (y[a] - m[3 + a]) * (x[b] - m[b]);
+}
+
 // The n points px fitted onto the n points py by the whole workgroup (NT threads, every thread gets the same Fit): the two means, the
 // covariance and its rotation, everything in double in a fixed order. SHORTCUT: point sets that are equal value for value are fitted by
 // the identity (Fit::same); without it same is false. red: NT / 64 doubles of LDS, sR: 9; both are free for the next use on return
@@ -43,10 +57,7 @@ __device__ __forceinline__ void kabsch_fit(PX px, PY py, int n, double* red, dou
         double x[3], y[3];
         px(k, x);
         py(k, y);
-        for (int c = 0; c < 3; ++c) {
-            m[c] += x[c]; m[3 + c] += y[c];
-            if (SHORTCUT) differ += x[c] == y[c] ? 0.0 : 1.0;
-        }
+        mean_terms<SHORTCUT>(x, y, m, differ);
     }
     for (int c = 0; c < 6; ++c) m[c] = block_sum<NT>(m[c], red) / (double)n;
     ft.same = false;
@@ -57,8 +68,7 @@ __device__ __forceinline__ void kabsch_fit(PX px, PY py, int n, double* red, dou
             double x[3], y[3];
             px(k, x);
             py(k, y);
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) H[3 * a + b] += (y[a] - m[3 + a]) * (x[b] - m[b]);
+            covariance_terms(x, y, m, H);
         }
         for (int c = 0; c < 9; ++c) H[c] = block_sum<NT>(H[c], red);
         if (threadIdx.x == 0) kabsch_rotation(H, sR);
@@ -93,6 +103,56 @@ __device__ __forceinline__ double moved_deviation(PX px, PY py, int n, const Fit
         }
     }
     return block_sum<NT>(dev, red);
+}
+
+// ------------------------------------------------------------------------------------------------ the fit of one wave on a subset
+// v summed (or its minimum taken) over the wave's 64 lanes by a fixed butterfly: the same bits in every lane, no barrier
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ double wave_min(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+
+// kabsch_fit by ONE wave on a subset of the n points (pesto_tmscore.hip): lane l owns the points l + 64 j and bit j of its word `in`
+// says whether point l + 64 j is fitted on (n <= 64 * 64; at least one point is). The same sums as kabsch_fit, over the members, by the
+// wave's butterfly; every lane then runs kabsch_rotation on the same bits, so every lane holds the same Fit and nothing goes through
+// LDS or a barrier: the waves of a workgroup fit independently.
+template <bool SHORTCUT, class PX, class PY>
+__device__ __forceinline__ void kabsch_fit_wave(PX px, PY py, int n, unsigned long long in, Fit& ft) {
+    const int lane = threadIdx.x & 63;
+    double* m = ft.m;
+    double differ = 0.0;
+    int members = 0;
+    for (int c = 0; c < 6; ++c) m[c] = 0.0;
+    for (int j = 0, k = lane; k < n; ++j, k += 64)
+        if (in >> j & 1ull) {
+            double x[3], y[3];
+            px(k, x);
+            py(k, y);
+            mean_terms<SHORTCUT>(x, y, m, differ);
+            ++members;
+        }
+    const double ns = (double)wave_sum(members);
+    for (int c = 0; c < 6; ++c) m[c] = wave_sum(m[c]) / ns;
+    ft.same = SHORTCUT && wave_sum(differ) == 0.0;
+    for (int c = 0; c < 9; ++c) ft.R[c] = c % 4 == 0 ? 1.0 : 0.0;
+    if (!ft.same) {
+        double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int j = 0, k = lane; k < n; ++j, k += 64)
+            if (in >> j & 1ull) {
+                double x[3], y[3];
+                px(k, x);
+                py(k, y);
+                covariance_terms(x, y, m, H);
+            }
+        for (int c = 0; c < 9; ++c) H[c] = wave_sum(H[c]);
+        kabsch_rotation(H, ft.R);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the RMSD after a fit
