@@ -877,6 +877,60 @@ int pesto_tmscore(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const 
                   float* gdt_ts_out, float* gdt_ha_out, int32_t* counts_out, float* rmsd_out, int32_t* seed_out, double* rotation_out,
                   double* translation_out, int32_t ptr_kind, void* stream);
 
+/* ---- pairwise sequence alignment, the alignment itself, and clustering by identity (pesto_align.hip) ----
+ * Failures of the entry points below are reported through pesto_align_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the TM-score group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ * replaces: what the package lacked between its dataset and its training - the sequence clusters that the reference's
+ * processing/split_dataset.ipynb downloads (RCSB's bc-30.out) - and a residue correspondence for two files numbered differently.
+ *
+ * Definition (pesto_amd/sequences.py states it in full). S sequences of codes in [0, A) lie back to back in codes uint8
+ * [seq_offsets[S]] (seq_offsets int32 [S + 1], HOST memory, from 0, 1 to PESTO_ALIGN_MAX_LENGTH codes each); matrix int8 [A, A] and pairs
+ * int32 [P, 2] (a before b, indices in [0, S)) are HOST memory too; PESTO_ALIGN_MAX_GAP >= gap_open >= gap_extend >= 0; unknown: a code that
+ * never counts as identical, or -1. For a of m codes against b of n, per cell (i, j) three int32 states,
+ *     D[i][j] = matrix[a[i-1]][b[j-1]] + max(D, U, L)[i-1][j-1]                          (mode 2, local: max(D, U, L, 0), a fresh start)
+ *     U[i][j] = max(D[i-1][j] - gap_open, U[i-1][j] - gap_extend, L[i-1][j] - gap_open)
+ *     L[i][j] = max(D[i][j-1] - gap_open, U[i][j-1] - gap_open, L[i][j-1] - gap_extend)
+ * THE FIRST IN THE ORDER D, U, L (then the fresh start) BEING THE PREDECESSOR ON TIES. mode 0, global: D[0][0] = 0, U[i][0] = L[0][i] =
+ * -(gap_open + (i - 1) gap_extend), the end at (m, n) in the best of D, U, L in that order. mode 1, overlap: D = 0 on both borders, the
+ * end the largest D over the cells with i = m or j = n, ties to the smallest i, then the smallest j. mode 2, local: the end the largest D
+ * over i, j >= 1 with the same rule; no positive D: the empty alignment (all zero). Everything else on the borders is minus infinity.
+ * The canonical alignment is the path from the end through those predecessors. Per pair, all int32:
+ *     score_out [P]; n_ident_out [P]: its D columns with equal codes other than `unknown`; n_aligned_out [P]: its D columns; n_cols_out
+ *     [P]: all its columns; span_out [P, 4] = (i0, j0, i1, j1), the half-open ranges of a and of b that it covers.
+ * Every output is an integer that depends on nothing but the pair: bit-identical from call to call. The codes are checked on the device
+ * (all below A) by a kernel whose verdict is read before anything is written; a refused call returns PESTO_ERR_INVALID. */
+const char* pesto_align_last_error(void);
+
+enum {
+    PESTO_ALIGN_MAX_LENGTH = 4096,            /* codes of a sequence: 13 bits for each count a state carries */
+    PESTO_ALIGN_MAX_ALPHABET = 32,            /* A */
+    PESTO_ALIGN_MAX_GAP = 127,                /* gap_open: with int8 scores every sum stays far inside int32 */
+    PESTO_ALIGN_MAX_SEQUENCES = 1 << 20,      /* S */
+    PESTO_ALIGN_MAX_PAIRS = 0x7fffffff,       /* P */
+    PESTO_ALIGN_MAX_MAP_PAIRS = 1 << 20,      /* P of the entry point that stores the alignments */
+    PESTO_ALIGN_MAPS_WORKSPACE = 1 << 28      /* bytes of predecessor choices (one per cell) held at a time; the list is run in chunks */
+};
+
+/* The five outputs of P pairs without any cell matrix: one wave per pair, lanes on strips of 8 columns skewed by a row, every state
+ * carrying its path's counts; O(m + n) memory per pair. pairs NULL: all i < j in row-major order (P = S (S - 1) / 2), decoded from a
+ * linear index - no list is made. labels_out int32 [S] or NULL: when given, the wave of a pair (a, b) links the two sequences as soon as
+ *     n_ident * 10000 >= id_bp * denom  and  n_aligned * 10000 >= cov_bp * max(m, n)      (64-bit integers; denom > 0)
+ * with denom by `over`: 0 = min(m, n), 1 = n_aligned, 2 = n_cols, and labels_out numbers the connected components in the order of their
+ * smallest members; the five per-pair outputs may then all be NULL. */
+int pesto_align_scores(pesto_model* m, int32_t S, const int32_t* seq_offsets, const uint8_t* codes, int32_t A, const int8_t* matrix, int32_t mode,
+                       int32_t gap_open, int32_t gap_extend, int32_t unknown, int64_t P, const int32_t* pairs, int32_t* score_out,
+                       int32_t* n_ident_out, int32_t* n_aligned_out, int32_t* n_cols_out, int32_t* span_out, int32_t id_bp, int32_t cov_bp,
+                       int32_t over, int32_t* labels_out, int32_t ptr_kind, void* stream);
+
+/* The same five outputs and the alignment of 1 <= P <= PESTO_ALIGN_MAX_MAP_PAIRS listed pairs: map_out int32 [sum of m over the list], per
+ * residue of a the index in b it is aligned to, -1 where it faces a gap or lies outside the span; pair p's rows follow pair p - 1's. The
+ * recursion stores one byte per cell (the three predecessor choices), the path is walked back on the device, and the counts are those met
+ * on the walk. */
+int pesto_align_maps(pesto_model* m, int32_t S, const int32_t* seq_offsets, const uint8_t* codes, int32_t A, const int8_t* matrix, int32_t mode,
+                     int32_t gap_open, int32_t gap_extend, int32_t unknown, int64_t P, const int32_t* pairs, int32_t* score_out, int32_t* n_ident_out,
+                     int32_t* n_aligned_out, int32_t* n_cols_out, int32_t* span_out, int32_t* map_out, int32_t ptr_kind, void* stream);
+
 /* ---- essential dynamics of MD frames: fluctuations, covariance, cross-correlation, principal components (Amadei et al. 1993) ----
  * Failures of the entry points below are reported through pesto_dynamics_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the cluster group they use the handle for its device, after

@@ -16,6 +16,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "dockq", "lrmsd", "fit_rmsd", "native_pairs", "capri_class",
            "lddt", "ilddt", "lddt_ca", "reference_pairs", "structure_lddt",
            "tmscore", "tm_score", "gdt", "tm_ca", "structure_tmscore",
+           "sequences", "align_scores", "align_maps", "cluster_sequences", "split_clusters", "structure_sequences",
            "dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
@@ -73,6 +74,10 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         tm = importlib.import_module(".tmscore", __name__)
         return tm if name == "tmscore" else getattr(tm, name)
+    if name in ("sequences", "align_scores", "align_maps", "cluster_sequences", "split_clusters", "structure_sequences"):
+        import importlib
+        sq = importlib.import_module(".sequences", __name__)
+        return sq if name == "sequences" else getattr(sq, name)
     if name in ("dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA"):
         import importlib
         dy = importlib.import_module(".dynamics", __name__)
