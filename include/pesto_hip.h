@@ -931,6 +931,65 @@ int pesto_align_maps(pesto_model* m, int32_t S, const int32_t* seq_offsets, cons
                      int32_t gap_open, int32_t gap_extend, int32_t unknown, int64_t P, const int32_t* pairs, int32_t* score_out, int32_t* n_ident_out,
                      int32_t* n_aligned_out, int32_t* n_cols_out, int32_t* span_out, int32_t* map_out, int32_t ptr_kind, void* stream);
 
+/* ---- structure-based alignment of CA traces: the alignment and the superposition found together (pesto_structalign.hip) ----
+ * Failures of the entry point below are reported through pesto_structalign_last_error() (thread-local message of the last failing call
+ * of this group; an invalid handle's message is copied there too). Like the align group it uses the handle for its device, after
+ * pesto_synchronize(m), allocates its buffers stream-ordered per call, keeps no state between calls and synchronises `stream`.
+ * replaces: what the package lacked for two chains whose residue correspondence is not known (a homologue, the two halves of a
+ * duplicated domain): outside the package, one run of a structure alignment program per pair. This is the library's OWN definition;
+ * no equality with the TM-align program is claimed.
+ *
+ * Definition (pesto_amd/structalign.py states it too). xyz float32 [offsets[S], 3]: the CA coordinates of S structures back to back
+ * (offsets int32 [S + 1], HOST memory, from 0; PESTO_STRUCTALIGN_MIN_LENGTH to PESTO_STRUCTALIGN_MAX_LENGTH residues each); pairs int32
+ * [P, 2], HOST memory: a of m residues is moved onto b of n residues; codes uint8 [offsets[S]] or NULL: residue codes, used only to count
+ * identities; init int32 [sum of m over the pairs] or NULL, HOST memory: the caller's initial map of every pair (-1, or indices of b that ascend);
+ * d0 double [P, 3], HOST memory: d0s of the pair (customarily the TM-score d0 of Lmin = min(m, n)), then the d0 of m and of n; scale
+ * turns coordinates into angstroms.
+ *   Cell score under a transform (R, t), in double from the float32 inputs: x'_i = x_i R + t, u = |x'_i - y_j|^2 scale^2 / d0s^2,
+ *     s_ij = int32(floor(Q / (1 + u) + 0.5)), Q = PESTO_STRUCTALIGN_Q.
+ *   DP(R, t, g): the recursion, ties D, U, L, end rule and canonical path of the align group in mode 1 (overlap), with s_ij in the place of
+ *     the matrix lookup, gap_open = g and gap_extend = 0: integer throughout. Its result is a map, its score and its n_aligned.
+ *   Initial alignments. I1, gapless threading: every offset k (a_i on b_(i+k)) whose overlap has at least max(3, ceil(Lmin / 2)) residues:
+ *     one fit (pesto_fit.h) of the overlap, the sum of s over the overlap under it; the largest sum wins, ties to the smallest k; the
+ *     alignment is the overlap. I2, fragments of f = min(Lmin, max(4, min(20, Lmin / 3))) residues starting at 0, stride, 2 stride, ...
+ *     <= len - f, plus len - f, stride = max(1, ceil((len - f) / (frag_starts - 1))): for every pair of fragments the fit of a's onto
+ *     b's, and the score of DP(fit, 0) of the whole chains; the largest score wins, ties to the lowest (start in a, start in b); the
+ *     alignment is the map of that DP. I3: init, if given.
+ *   Units. A unit is (initial alignment i, gap g) with g = round(gap_open Q), then 0: unit 2 i + (g == 0), 4 or 6 per pair. A unit whose
+ *     alignment has fewer than 3 pairs is dead. In each of `rounds` rounds a live unit (1) runs the TM-score search of the tmscore group
+ *     on its aligned pairs (a's residues onto b's, norm_len = Lmin, d0 = d0s, step = max(1, n_aligned >> 3), n_iter 20): tm_r, R, t;
+ *     (2) runs DP(R, t, its gap): the new map; (3) is done if the new map equals the old one, dead if it aligns fewer than 3 pairs.
+ *   The pair's result is the alignment SEARCHED in the (unit, round) with the largest tm_r (float32), ties to the lowest (unit, round).
+ * Outputs per pair: map_out int32 [sum of m]: the index in b or -1; n_aligned_out, n_ident_out (aligned pairs with equal codes; 0 without
+ * codes), dp_score_out (the score of the winning round's DP), unit_out, round_out int32 [P]; tm_out float32 [P, 2]: the winning pairs
+ * scored by the tmscore group at step 1, normalised by m with d0[1] and by n with d0[2], bit for bit what pesto_tmscore gives for them;
+ * rotation_out double [P, 3, 3], translation_out double [P, 3]: those of the search normalised by the shorter chain (the first with m =
+ * n); rmsd_out float32 [P]: over the aligned pairs, as pesto_tmscore reports it; history_out double [P, units, rounds, 3] = (tm_r, the
+ * score of the round's DP, n_aligned of the alignment searched), NaN where a unit did not run.
+ * No unit ever alive: tm 0, n_aligned 0, map -1, the identity transform, rmsd NaN, unit and round -1. A non-finite coordinate in either
+ * chain: NaN scores and transform, map -1, unit -1. Every argument is checked on the host before any launch; a refused call returns
+ * PESTO_ERR_INVALID and writes nothing. No atomics, and nothing depends on how the work is shared over workgroups: every output is
+ * bit-identical from call to call and between host and device inputs. The host reads every unit's n_aligned and done flag once per
+ * round (8 bytes a unit) to lay out the next round's ragged batch. */
+const char* pesto_structalign_last_error(void);
+
+enum {
+    PESTO_STRUCTALIGN_Q = 1024,               /* the score of two residues in the same place */
+    PESTO_STRUCTALIGN_MIN_LENGTH = 3,         /* residues of a chain: a superposition needs three points */
+    PESTO_STRUCTALIGN_MAX_LENGTH = 4096,      /* ... and the TM search keeps 64 points a lane */
+    PESTO_STRUCTALIGN_MAX_STRUCTURES = 1 << 20,
+    PESTO_STRUCTALIGN_MAX_PAIRS = 1 << 20,    /* P */
+    PESTO_STRUCTALIGN_MAX_ROUNDS = 64,
+    PESTO_STRUCTALIGN_MIN_FRAG_STARTS = 2,
+    PESTO_STRUCTALIGN_MAX_FRAG_STARTS = 64,
+    PESTO_STRUCTALIGN_WORKSPACE = 1 << 28     /* bytes of predecessor choices (one per cell) held at a time; the units run in chunks */
+};
+
+int pesto_structalign(pesto_model* m, int32_t S, const int32_t* offsets, const float* xyz, const uint8_t* codes, int64_t P, const int32_t* pairs,
+                      const int32_t* init, const double* d0, double gap_open, int32_t rounds, int32_t frag_starts, double scale, int32_t* map_out,
+                      int32_t* n_aligned_out, int32_t* n_ident_out, int32_t* dp_score_out, int32_t* unit_out, int32_t* round_out, float* tm_out,
+                      double* rotation_out, double* translation_out, float* rmsd_out, double* history_out, int32_t ptr_kind, void* stream);
+
 /* ---- essential dynamics of MD frames: fluctuations, covariance, cross-correlation, principal components (Amadei et al. 1993) ----
  * Failures of the entry points below are reported through pesto_dynamics_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the cluster group they use the handle for its device, after

@@ -15,7 +15,8 @@
 // the row above and U of the row below (likewise a function of the row above alone): 7 registers per column with the code of b.
 // Sequences longer than one pass of 64 strips (512 columns) run in column blocks; the block's last column goes through the call's
 // allocation, 24 bytes per row and wave (lane 63 stores row i, lane 0 of the next block loads it one step ahead of its use).
-// The substitution matrix (row stride 32) and the wave's two sequences sit in LDS.
+// The substitution matrix (row stride 32) and the wave's two sequences sit in LDS. The recursion itself (align_wave) lives in
+// pesto_alignwave.h, templated on the score source, and is shared with pesto_structalign.hip; here the source is the matrix lookup.
 // k_align<MODE, true> is the same recursion storing every cell's three predecessor choices as one byte; lane 0 then walks the canonical
 // path back and writes `map` and the counts IT meets, so the equality of the two kernels' outputs is a test of the carries.
 //
@@ -26,30 +27,22 @@
 #include <cmath>
 #include <numeric>
 
+#include "pesto_alignwave.h"
 #include "pesto_call.h"
 
 namespace pesto {
 
 namespace {
 
+using namespace wave;
+
 constexpr int NT = 256;                         // threads per workgroup
 constexpr int NW = NT / 64;                     // its waves: a pair each
-constexpr int W = 8;                            // columns of a lane's strip
-constexpr int BLOCK_COLS = 64 * W;              // columns of one pass
 constexpr int MAXLEN = PESTO_ALIGN_MAX_LENGTH;
 constexpr int STRIDE = PESTO_ALIGN_MAX_ALPHABET;    // row stride of the matrix in LDS
-constexpr int NEG = -(1 << 29);                 // minus infinity: real scores stay within +-(127 * 8192 + 127 * 8193), and so does the drift
-                                                // of what derives from NEG, so it neither overflows nor wins
-constexpr unsigned HI_MASK = 0x03ffffffu;       // i0 | j0 << 13 of a carry's second dword; bits 26-27: which state a maximum took
 constexpr int MAX_SLOTS = 4096;                 // waves of one launch
 constexpr size_t BOUND_CAP = (size_t)256 << 20; // bytes of the column-block boundary rows of one launch (at least 256 waves' worth)
-constexpr int ROW_INTS = 6;                     // a boundary row: M and L, value and two carry dwords each
-
-enum { MODE_GLOBAL = 0, MODE_OVERLAP = 1, MODE_LOCAL = 2 };
 enum { OVER_SHORTER = 0, OVER_ALIGNED = 1, OVER_COLUMNS = 2 };
-
-// a state's value and the counts of its canonical path: lo = n_ident | n_aligned << 13, hi = i0 | j0 << 13
-struct Cell { int v; unsigned lo, hi; };
 
 struct AlignArgs {
     int S, mode, go, ge, unknown, A;
@@ -70,9 +63,6 @@ struct AlignArgs {
     const long long* map_off;                   // [P]
     const int* err;
 };
-
-__device__ __forceinline__ int ldg(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void stg(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ------------------------------------------------------------------------------------------------ union-find
 // Every value an entry ever holds is a member of its set with an index below the entry's own or the entry itself (links put a root under
@@ -100,145 +90,22 @@ __device__ __forceinline__ void set_link(int* par, int a, int b) {
 }
 
 // ------------------------------------------------------------------------------------------------ the recursion
-// the best of a - pa, b - pb, c - pc, the first on ties, with its carry (and, for the traceback, which one in bits 26-27 of hi)
-template <bool TRACE>
-__device__ __forceinline__ Cell best3(const Cell& a, int pa, const Cell& b, int pb, const Cell& c, int pc) {
-    Cell r = a;
-    r.v = a.v - pa;
-    unsigned arg = 0;
-    const int bv = b.v - pb, cv = c.v - pc;
-    if (bv > r.v) { r = b; r.v = bv; arg = 1; }
-    if (cv > r.v) { r = c; r.v = cv; arg = 2; }
-    if (TRACE) r.hi |= arg << 26;
-    return r;
-}
-
-// the states of the border cells (0, j) and (i, 0)
-template <int MODE>
-__device__ __forceinline__ void border(int i, int j, int go, int ge, Cell& D, Cell& U, Cell& L) {
-    D = U = L = Cell{NEG, 0u, 0u};
-    if (MODE == MODE_GLOBAL) {
-        if (i == 0 && j == 0) D.v = 0;
-        else if (i == 0) L.v = -(go + (j - 1) * ge);
-        else U.v = -(go + (i - 1) * ge);
-    } else if (MODE == MODE_OVERLAP) {
-        D.v = 0;
-        D.hi = (unsigned)i | (unsigned)j << 13;
+// align_wave of pesto_alignwave.h with this score source: the substitution matrix (row stride 32) and the wave's two sequences in LDS;
+// a lane keeps the codes of its strip's columns in registers and looks a row of the matrix up once per row.
+struct MatrixScore {
+    typedef int Col;
+    struct Row { int ac; const int8_t* row; };
+    const uint8_t *sa, *sb;
+    const int8_t* smat;
+    int unknown;
+    __device__ __forceinline__ Col column(int j, int n) const { return j <= n ? sb[j - 1] : 0; }
+    __device__ __forceinline__ Row row(int i) const {
+        const int ac = sa[i - 1];
+        return Row{ac, smat + ac * STRIDE};
     }
-}
-
-__device__ __forceinline__ Cell shift_up(const Cell& c) { return Cell{__shfl_up(c.v, 1), __shfl_up(c.lo, 1), __shfl_up(c.hi, 1)}; }
-
-// (v, i, j) ordered as the end rule has it: the larger value, then the smaller i, then the smaller j
-__device__ __forceinline__ bool ends_before(int v, int i, int j, int v2, int i2, int j2) { return v > v2 || (v == v2 && (i < i2 || (i == i2 && j < j2))); }
-
-struct End { int v, i, j; unsigned lo, hi; };
-
-// One wave, one pair: a (m codes at sa) against b (n codes at sb), both and the matrix in LDS. Returns the end cell of the canonical path
-// with its value and carry in every lane (for MODE_GLOBAL hi keeps the end's state in bits 26-27 when TRACE).
-template <int MODE, bool TRACE>
-__device__ End align_wave(const uint8_t* sa, const uint8_t* sb, const int8_t* smat, int m, int n, int go, int ge, int unknown, int* bound, uint8_t* tb) {
-    const int lane = threadIdx.x & 63;
-    End best{INT_MIN, 0, 0, 0u, 0u};
-    for (int jb = 0; jb < n; jb += BLOCK_COLS) {
-        const bool first = jb == 0, more = jb + BLOCK_COLS < n;
-        const int j0 = jb + lane * W;           // the strip is columns j0 + 1 .. j0 + W
-        const int n_act = min(64, (n - jb + W - 1) / W);
-        Cell Mp[W], Un[W];
-        int bc[W];
-#pragma unroll
-        for (int c = 0; c < W; ++c) {
-            const int j = j0 + c + 1;
-            bc[c] = j <= n ? sb[j - 1] : 0;
-            Cell D, U, L;
-            border<MODE>(0, j, go, ge, D, U, L);
-            Mp[c] = best3<TRACE>(D, 0, U, 0, L, 0);
-            Un[c] = best3<TRACE>(D, go, U, ge, L, go);
-        }
-        Cell dsave;                             // M[i - 1][j0] for the row the lane is about to do
-        {
-            Cell D, U, L;
-            border<MODE>(0, j0, go, ge, D, U, L);
-            dsave = best3<TRACE>(D, 0, U, 0, L, 0);
-        }
-        End blk{INT_MIN, 0, 0, 0u, 0u};
-        Cell sendM{NEG, 0u, 0u}, sendL{NEG, 0u, 0u}, nextM{NEG, 0u, 0u}, nextL{NEG, 0u, 0u};
-        auto load_row = [&](int i) {
-            const int* r = bound + (size_t)i * ROW_INTS;
-            nextM = Cell{ldg(r), (unsigned)ldg(r + 1), (unsigned)ldg(r + 2)};
-            nextL = Cell{ldg(r + 3), (unsigned)ldg(r + 4), (unsigned)ldg(r + 5)};
-        };
-        if (!first && lane == 0) load_row(1);
-        const int steps = m + n_act - 1;
-        for (int t = 1; t <= steps; ++t) {
-            const int i = t - lane;
-            Cell inM = shift_up(sendM), inL = shift_up(sendL);
-            if (lane == 0) {
-                if (first) {
-                    Cell D, U, L;
-                    border<MODE>(min(t, m), 0, go, ge, D, U, L);
-                    inM = best3<TRACE>(D, 0, U, 0, L, 0);
-                    inL = best3<TRACE>(D, go, U, go, L, ge);
-                } else {
-                    inM = nextM;
-                    inL = nextL;
-                    if (t < m) load_row(t + 1);
-                }
-            }
-            if (i >= 1 && i <= m) {
-                Cell diag = dsave, Lc = inL;
-                dsave = inM;
-                const int ac = sa[i - 1];
-                const int8_t* row = smat + ac * STRIDE;
-#pragma unroll
-                for (int c = 0; c < W; ++c) {
-                    const int j = j0 + c + 1;
-                    const Cell above = Mp[c];
-                    const int s = row[bc[c]];
-                    Cell D{diag.v + s, diag.lo, TRACE ? diag.hi & HI_MASK : diag.hi};
-                    unsigned pD = diag.hi >> 26;
-                    if (MODE == MODE_LOCAL && diag.v < 0) {         // the fresh start is the last candidate: only below zero
-                        D = Cell{s, 0u, (unsigned)(i - 1) | (unsigned)(j - 1) << 13};
-                        pD = 3;
-                    }
-                    D.lo += (1u << 13) + ((ac == bc[c] && ac != unknown) ? 1u : 0u);
-                    Cell U = Un[c], L = Lc;
-                    if (TRACE) {
-                        const unsigned pU = U.hi >> 26, pL = L.hi >> 26;
-                        U.hi &= HI_MASK;
-                        L.hi &= HI_MASK;
-                        if (j <= n) tb[(size_t)(i - 1) * n + (j - 1)] = (uint8_t)(pD | pU << 2 | pL << 4);
-                    }
-                    const Cell M = best3<TRACE>(D, 0, U, 0, L, 0);
-                    Un[c] = best3<TRACE>(D, go, U, ge, L, go);
-                    Lc = best3<TRACE>(D, go, U, go, L, ge);
-                    Mp[c] = M;
-                    diag = above;
-                    if (MODE == MODE_GLOBAL) {
-                        if (i == m && j == n) blk = End{M.v, i, j, M.lo, M.hi};
-                    } else {                                        // rows, then columns ascend: the first maximum met is the rule's
-                        const bool cand = MODE == MODE_LOCAL ? j <= n : (j == n || (i == m && j < n));
-                        if (cand && D.v > blk.v) blk = End{D.v, i, j, D.lo, D.hi};
-                    }
-                }
-                sendM = Mp[W - 1];
-                sendL = Lc;
-                if (more && lane == 63) {
-                    int* r = bound + (size_t)i * ROW_INTS;
-                    stg(r, sendM.v); stg(r + 1, (int)sendM.lo); stg(r + 2, (int)sendM.hi);
-                    stg(r + 3, sendL.v); stg(r + 4, (int)sendL.lo); stg(r + 5, (int)sendL.hi);
-                }
-            }
-        }
-        if (ends_before(blk.v, blk.i, blk.j, best.v, best.i, best.j)) best = blk;
-        if (more) __threadfence();
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const End e{__shfl_xor(best.v, o), __shfl_xor(best.i, o), __shfl_xor(best.j, o), __shfl_xor(best.lo, o), __shfl_xor(best.hi, o)};
-        if (ends_before(e.v, e.i, e.j, best.v, best.i, best.j)) best = e;
-    }
-    return best;
-}
+    __device__ __forceinline__ int score(const Row& r, Col bc) const { return r.row[bc]; }
+    __device__ __forceinline__ bool ident(const Row& r, Col bc) const { return r.ac == bc && r.ac != unknown; }
+};
 
 // pair `p` of all i < j in row-major order, S sequences
 __device__ __forceinline__ long long pair_position(long long i, long long j, long long S) { return i * (2 * S - i - 1) / 2 + (j - i - 1); }
@@ -287,7 +154,8 @@ __global__ __launch_bounds__(NT, 3) void k_align(const AlignArgs A) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         uint8_t* tb = TRACE ? A.tb + A.tb_off[p] : nullptr;
-        const End e = align_wave<MODE, TRACE>(sa, sb, s_mat, m, n, A.go, A.ge, A.unknown, bound, tb);
+        const MatrixScore src{sa, sb, s_mat, A.unknown};
+        const End e = align_wave<MODE, TRACE>(src, m, n, A.go, A.ge, bound, tb);
         // the end rule's border cells: an overlap end (0, n) of value 0 precedes every cell of a row i >= 1 that does not beat it
         const bool empty = (MODE == MODE_OVERLAP || MODE == MODE_LOCAL) && e.v <= 0;
         int score = empty ? 0 : e.v, i1 = empty ? 0 : e.i, j1 = empty ? (MODE == MODE_OVERLAP ? n : 0) : e.j;
@@ -296,6 +164,9 @@ __global__ __launch_bounds__(NT, 3) void k_align(const AlignArgs A) {
         if (TRACE) {
             int* map = A.map + A.map_off[p];
             __threadfence();
+            // (not walk_back of pesto_alignwave.h: this walk starts in the END STATE of a global alignment, fills the rows a global path
+            // leaves above its first cell, and counts the identities it meets from the two sequences, so that its five outputs test the
+            // carries of k_align<MODE, false>; walk_back is the overlap / local walk of a source without an identity)
             if (lane == 0 && !empty) {                              // the canonical path, back from the end
                 int i = i1, j = j1, ni = 0, na = 0;
                 unsigned st = e.hi >> 26;

@@ -16,6 +16,7 @@
 
 #include "pesto_call.h"
 #include "pesto_fit.h"
+#include "pesto_tmsearch.h"
 
 namespace pesto {
 
@@ -23,29 +24,14 @@ namespace {
 
 constexpr int NT = 256;                 // threads per workgroup of k_tm_search
 constexpr int NW = NT / 64;             // its waves
-constexpr int MAX_LENGTHS = 7;          // window lengths L >> 0 .. 5, then min(L, 4)
-constexpr int N_CUT = 5;                // GDT cut-offs
 constexpr int TARGET_GROUPS = 1024;     // workgroups a call aims at, so that one model still fills the device
 constexpr int SEED_NONE = INT_MAX;      // TmBest::seed of a share without seeds
 constexpr int SEED_BAD = -1;            // ... of a frame with a non-finite selected coordinate
 
-// one structure of the call: its range of sel, its seeds (cnt[l] windows of length len[l], numbered length first, then start) and its
-// constants
-struct TmStruct {
-    int s0, L, n_len, n_seeds;
-    int len[MAX_LENGTHS], cnt[MAX_LENGTHS];
-    double d0, lnorm, d_search;
-};
-
-// what a share found: the best TM sum over its visited fits with its seed and fit (x' = x R + t), and the largest counts
-struct TmBest {
-    double tm, R[9], t[3];
-    int seed, cnt[N_CUT];
-};
-
 // the seeds of a structure of L points: the lengths L >> k while above 4, then min(L, 4); the starts 0, step, 2 step, ... <= L - n and
 // L - n itself
 void plan_seeds(int L, int step, TmStruct& s) {
+    s.step = step;
     s.n_len = 0;
     s.n_seeds = 0;
     auto add = [&](int n) {
@@ -61,7 +47,7 @@ void plan_seeds(int L, int step, TmStruct& s) {
 // ------------------------------------------------------------------------------------------------ the search
 // replaces: the TMscore program's superposition search, one model per process. Workgroup (unit u, share sh): unit = frame, or structure of
 // a ragged batch (n_struct > 1: one frame). Wave w of share sh runs the seeds sh NW + w, + shares NW, ... of its unit.
-__global__ __launch_bounds__(NT) void k_tm_search(int shares, int N, int n_struct, int step, int n_iter, int max_raise, double scale,
+__global__ __launch_bounds__(NT) void k_tm_search(int shares, int N, int n_struct, int n_iter, int max_raise, double scale,
                                                   const TmStruct* __restrict__ structs, const float* __restrict__ ref, const float* __restrict__ xyz,
                                                   const int* __restrict__ sel, const int* __restrict__ err, TmBest* __restrict__ out) {
     extern __shared__ float s_pts[];            // the frame's L points, then the reference's
@@ -70,7 +56,7 @@ __global__ __launch_bounds__(NT) void k_tm_search(int shares, int N, int n_struc
     const unsigned u = blockIdx.x / (unsigned)shares, sh = blockIdx.x % (unsigned)shares;
     const TmStruct& S = structs[n_struct > 1 ? u : 0];
     const float* X = xyz + (n_struct > 1 ? (size_t)0 : (size_t)u * N * 3);
-    const int L = S.L;
+    const int L = S.L, step = S.step;
     float* sx = s_pts;
     float* sy = s_pts + 3 * (size_t)L;
     int bad = 0;
@@ -91,13 +77,13 @@ __global__ __launch_bounds__(NT) void k_tm_search(int shares, int N, int n_struc
     const auto px = atoms<true>(sx, nullptr), py = atoms<true>(sy, nullptr);
     const double d0 = S.d0, d_search = S.d_search;
     const int need = L < 3 ? L : 3;
-    const double cuts[N_CUT] = {0.5, 1.0, 2.0, 4.0, 8.0};
+    const double cuts[TM_N_CUT] = {0.5, 1.0, 2.0, 4.0, 8.0};
     TmBest best;
     best.tm = -1.0;
     best.seed = SEED_NONE;
     for (int c = 0; c < 9; ++c) best.R[c] = 0.0;
     for (int c = 0; c < 3; ++c) best.t[c] = 0.0;
-    for (int c = 0; c < N_CUT; ++c) best.cnt[c] = 0;
+    for (int c = 0; c < TM_N_CUT; ++c) best.cnt[c] = 0;
 
     for (int seed = (int)sh * NW + wave; seed < S.n_seeds; seed += shares * NW) {
         int n = 0, start = 0;
@@ -132,18 +118,18 @@ __global__ __launch_bounds__(NT) void k_tm_search(int shares, int N, int n_struc
                     if (tsum) {
                         const double q = d / d0;
                         *tsum += 1.0 / (1.0 + q * q);
-                        for (int c = 0; c < N_CUT; ++c) cnt[c] += d < cuts[c] ? 1 : 0;
+                        for (int c = 0; c < TM_N_CUT; ++c) cnt[c] += d < cuts[c] ? 1 : 0;
                     }
                 }
                 lowest = wave_min(lowest);
                 return wave_sum(ns);
             };
             double d_cut = d_search, lowest, tsum = 0.0;
-            int cnt[N_CUT] = {0, 0, 0, 0, 0};
+            int cnt[TM_N_CUT] = {0, 0, 0, 0, 0};
             unsigned long long next;
             int ns = members(d_cut, next, lowest, &tsum, cnt);
             tsum = wave_sum(tsum);                      // (the quotient by L_norm is taken once, in k_tm_final)
-            for (int c = 0; c < N_CUT; ++c) best.cnt[c] = max(best.cnt[c], wave_sum(cnt[c]));
+            for (int c = 0; c < TM_N_CUT; ++c) best.cnt[c] = max(best.cnt[c], wave_sum(cnt[c]));
             if (tsum > best.tm) {                       // (a wave meets its seeds in ascending order: the first to attain the maximum stays)
                 best.tm = tsum;
                 best.seed = seed;
@@ -167,11 +153,11 @@ __global__ __launch_bounds__(NT) void k_tm_search(int shares, int N, int n_struc
     if (threadIdx.x == 0) {
         for (int w = 1; w < NW; ++w) {
             const TmBest& o = s_best[w];
-            for (int c = 0; c < N_CUT; ++c) best.cnt[c] = max(best.cnt[c], o.cnt[c]);
+            for (int c = 0; c < TM_N_CUT; ++c) best.cnt[c] = max(best.cnt[c], o.cnt[c]);
             if (o.tm > best.tm || (o.tm == best.tm && o.seed < best.seed)) {
-                const int keep[N_CUT] = {best.cnt[0], best.cnt[1], best.cnt[2], best.cnt[3], best.cnt[4]};
+                const int keep[TM_N_CUT] = {best.cnt[0], best.cnt[1], best.cnt[2], best.cnt[3], best.cnt[4]};
                 best = o;
-                for (int c = 0; c < N_CUT; ++c) best.cnt[c] = keep[c];
+                for (int c = 0; c < TM_N_CUT; ++c) best.cnt[c] = keep[c];
             }
         }
         out[blockIdx.x] = best;
@@ -192,31 +178,59 @@ __global__ __launch_bounds__(64) void k_tm_final(int shares, int n_struct, const
     const int lane = threadIdx.x;
     const bool bad = P[0].seed == SEED_BAD;             // (every share of the unit saw the same points)
     double tm = -1.0;
-    int seed = SEED_NONE, at = 0, cnt[N_CUT] = {0, 0, 0, 0, 0};
+    int seed = SEED_NONE, at = 0, cnt[TM_N_CUT] = {0, 0, 0, 0, 0};
     if (!bad)
         for (int s = lane; s < shares; s += 64) {
             const TmBest& o = P[s];
-            for (int c = 0; c < N_CUT; ++c) cnt[c] = max(cnt[c], o.cnt[c]);
+            for (int c = 0; c < TM_N_CUT; ++c) cnt[c] = max(cnt[c], o.cnt[c]);
             if (o.tm > tm || (o.tm == tm && o.seed < seed)) { tm = o.tm; seed = o.seed; at = s; }
         }
     for (int o = 32; o > 0; o >>= 1) {
         const double tm2 = __shfl_xor(tm, o);
         const int seed2 = __shfl_xor(seed, o), at2 = __shfl_xor(at, o);
         if (tm2 > tm || (tm2 == tm && (seed2 < seed || (seed2 == seed && at2 < at)))) { tm = tm2; seed = seed2; at = at2; }
-        for (int c = 0; c < N_CUT; ++c) cnt[c] = max(cnt[c], __shfl_xor(cnt[c], o));
+        for (int c = 0; c < TM_N_CUT; ++c) cnt[c] = max(cnt[c], __shfl_xor(cnt[c], o));
     }
     if (lane != 0) return;
     const double nan = NAN, four_L = 4.0 * (double)S.L;
     tm_out[u] = bad ? NAN : (float)(tm / S.lnorm);
     ts_out[u] = bad ? NAN : (float)((double)(cnt[1] + cnt[2] + cnt[3] + cnt[4]) / four_L);
     ha_out[u] = bad ? NAN : (float)((double)(cnt[0] + cnt[1] + cnt[2] + cnt[3]) / four_L);
-    for (int c = 0; c < N_CUT; ++c) counts_out[u * N_CUT + c] = bad ? 0 : cnt[c];
+    for (int c = 0; c < TM_N_CUT; ++c) counts_out[u * TM_N_CUT + c] = bad ? 0 : cnt[c];
     seed_out[u] = bad ? -1 : seed;
     for (int c = 0; c < 9; ++c) rot_out[u * 9 + c] = bad ? nan : P[at].R[c];
     for (int c = 0; c < 3; ++c) tr_out[u * 3 + c] = bad ? nan : P[at].t[c];
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------ what pesto_structalign.hip shares
+// (pesto_tmsearch.h: the structure alignment runs this very search on the pairs it has aligned, round after round)
+void tm_plan(int s0, int L, int step, double norm_len, double d0, TmStruct& s) {
+    s.s0 = s0;
+    s.L = L;
+    plan_seeds(L, step, s);
+    s.d0 = d0;
+    s.lnorm = norm_len;
+    s.d_search = std::min(8.0, std::max(4.5, d0));
+}
+
+int tm_shares(int seeds_max, int64_t U) {
+    return (int)std::min<int64_t>((seeds_max + NW - 1) / NW, std::max<int64_t>(1, (TARGET_GROUPS + U - 1) / U));
+}
+
+hipError_t tm_search_launch(hipStream_t stm, int64_t U, int64_t N, int n_struct, int shares, int L_max, int n_iter, double scale, const TmStruct* structs,
+                            const float* ref, const float* xyz, const int* sel, const int* err, TmBest* parts, float* tm_out, float* ts_out, float* ha_out,
+                            int* counts_out, int* seed_out, double* rot_out, double* tr_out) {
+    const size_t smem = (size_t)L_max * 24;
+    if (hipError_t e = hipFuncSetAttribute((const void*)k_tm_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)) return e;
+    hipLaunchKernelGGL(k_tm_search, dim3((unsigned)(U * shares)), dim3(NT), smem, stm, shares, (int)N, n_struct, n_iter, (int)PESTO_TMSCORE_MAX_RAISE, scale,
+                       structs, ref, xyz, sel, err, parts);
+    hipLaunchKernelGGL(k_tm_final, dim3((unsigned)U), dim3(64), 0, stm, shares, n_struct, structs, (const TmBest*)parts, err, tm_out, ts_out, ha_out,
+                       counts_out, seed_out, rot_out, tr_out);
+    return hipSuccess;
+}
+
 }  // namespace pesto
 
 using namespace pesto;
@@ -244,39 +258,31 @@ int pesto_tmscore(pesto_model* m, int64_t F, int64_t N, int32_t n_struct, const 
         if (!(std::isfinite(norm_len[b]) && norm_len[b] > 0.0) || !(std::isfinite(d0[b]) && d0[b] > 0.0))
             return fail(PESTO_ERR_INVALID, "structure %d: norm_len and d0 must be positive and finite", b);
         TmStruct& s = st[(size_t)b];
-        s.s0 = sel_offsets[b];
-        s.L = (int)L;
-        plan_seeds((int)L, step, s);
-        s.d0 = d0[b];
-        s.lnorm = norm_len[b];
-        s.d_search = std::min(8.0, std::max(4.5, d0[b]));
+        tm_plan(sel_offsets[b], (int)L, step, norm_len[b], d0[b], s);
         L_max = std::max(L_max, s.L);
         seeds_max = std::max(seeds_max, s.n_seeds);
     }
     if (int rc = begin(m, ptr_kind)) return rc;
     const int64_t n_sel = sel_offsets[n_struct], U = n_struct > 1 ? n_struct : F;
-    const int shares = (int)std::min<int64_t>((seeds_max + NW - 1) / NW, std::max<int64_t>(1, (TARGET_GROUPS + U - 1) / U));
+    const int shares = tm_shares(seeds_max, U);
     Buffers bf(ptr_kind, stream);
     const int iY = bf.input(xyz_ref, (size_t)N * 12), iX = bf.input(xyz, (size_t)F * N * 12), iS = bf.input(sel, (size_t)n_sel * 4);
     const int iT = bf.table(st.data(), st.size() * sizeof(TmStruct));
     const int iTm = bf.output(tm_out, (size_t)U * 4), iTs = bf.output(gdt_ts_out, (size_t)U * 4), iHa = bf.output(gdt_ha_out, (size_t)U * 4),
-              iCn = bf.output(counts_out, (size_t)U * N_CUT * 4), iRm = bf.output(rmsd_out, (size_t)U * 4), iSd = bf.output(seed_out, (size_t)U * 4),
+              iCn = bf.output(counts_out, (size_t)U * TM_N_CUT * 4), iRm = bf.output(rmsd_out, (size_t)U * 4), iSd = bf.output(seed_out, (size_t)U * 4),
               iRo = bf.output(rotation_out, (size_t)U * 72), iTr = bf.output(translation_out, (size_t)U * 24);
     const int iP = bf.scratch((size_t)U * shares * sizeof(TmBest)), iSt = bf.scratch(sizeof(int), 0);
     int herr = 0;
     int rc = bf.upload();
-    const size_t smem = (size_t)L_max * 24;
-    if (rc == 0) rc = hip_ok(hipFuncSetAttribute((const void*)k_tm_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), "tmscore");
     if (rc == 0) {
         const IndexLists idx = {{bf.ptr<const int>(iS)}, {n_sel}};
-        const TmStruct* sd = bf.ptr<const TmStruct>(iT);
         hipLaunchKernelGGL(k_index_check<NT>, dim3(blocks((size_t)idx.total(), NT)), dim3(NT), 0, bf.stm, (int)N, idx, bf.ptr<int>(iSt));
-        hipLaunchKernelGGL(k_tm_search, dim3((unsigned)(U * shares)), dim3(NT), smem, bf.stm, shares, (int)N, (int)n_struct, (int)step, (int)n_iter,
-                           (int)PESTO_TMSCORE_MAX_RAISE, scale, sd, bf.ptr<const float>(iY), bf.ptr<const float>(iX), bf.ptr<const int>(iS),
-                           bf.ptr<const int>(iSt), bf.ptr<TmBest>(iP));
-        hipLaunchKernelGGL(k_tm_final, dim3((unsigned)U), dim3(64), 0, bf.stm, shares, (int)n_struct, sd, bf.ptr<const TmBest>(iP), bf.ptr<const int>(iSt),
-                           bf.ptr<float>(iTm), bf.ptr<float>(iTs), bf.ptr<float>(iHa), bf.ptr<int>(iCn), bf.ptr<int>(iSd), bf.ptr<double>(iRo),
-                           bf.ptr<double>(iTr));
+        rc = hip_ok(tm_search_launch(bf.stm, U, N, (int)n_struct, shares, L_max, (int)n_iter, scale, bf.ptr<const TmStruct>(iT), bf.ptr<const float>(iY),
+                                     bf.ptr<const float>(iX), bf.ptr<const int>(iS), bf.ptr<const int>(iSt), bf.ptr<TmBest>(iP), bf.ptr<float>(iTm),
+                                     bf.ptr<float>(iTs), bf.ptr<float>(iHa), bf.ptr<int>(iCn), bf.ptr<int>(iSd), bf.ptr<double>(iRo), bf.ptr<double>(iTr)),
+                    "tmscore");
+    }
+    if (rc == 0) {
         // rmsd: pesto_fit_rmsd's kernel on sel for fit and measure, a structure of a ragged batch at a time
         for (int b = 0; b < n_struct; ++b) {
             const int* sl = bf.ptr<const int>(iS) + st[(size_t)b].s0;

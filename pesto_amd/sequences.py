@@ -62,7 +62,7 @@ integer test on the host) or if o has any link, and otherwise stay alone, as o d
 min(m, n) * 10000 < cov_bp * max(m, n) are not enumerated, because n_aligned <= min(m, n).
 Neither changes labels. There is no k-mer or other inexact prefilter.
 
-Not built: structure-based alignment (TM-align), profile or multiple alignment, k-mer prefilters and database-scale search, nucleic
+Not built (structure-based alignment is structalign.py's): profile or multiple alignment, k-mer prefilters and database-scale search, nucleic
 acids, sequences above 4096, packed 16-bit arithmetic, chain permutation beyond the greedy pairing of match_atoms.
 
 Limits: 1 <= length <= MAX_LENGTH, A <= 32, gap_open <= 127, S <= 2**20, at most 2**31 - 1 pairs per call (2**20 for align_maps).
@@ -465,7 +465,9 @@ def match_atoms(reference, predicted, model=None):
     return _matched(reference, predicted, model)[:5]
 
 
-def _matched(reference, predicted, model=None):
+def _matched(reference, predicted, model=None, partner_of=None):
+    """partner_of: (a, b, fa, fb) -> the model's residue row under every reference row (structalign.structure_align pairs the residues by
+    structure); None: by sequence alignment, as match_atoms states"""
     from .lddt import _structure_dict
     a, b = _structure_dict(reference), _structure_dict(predicted)
     fa, cha, _, _ = _residues(a)
@@ -476,7 +478,9 @@ def _matched(reference, predicted, model=None):
     row_of_a = {int(f): r for r, f in enumerate(fa)}
     row_of_b = {int(f): r for r, f in enumerate(fb)}
     partner = np.full(fa.size, -1, np.int64)            # the model's residue row under every reference row
-    if sa and sb:
+    if partner_of is not None:
+        partner = np.asarray(partner_of(a, b, fa, fb), np.int64)
+    elif sa and sb:
         seqs = [s[1] for s in sa] + [s[1] for s in sb]
         na, nb = len(sa), len(sb)
         pairs = np.array([(i, na + j) for i in range(na) for j in range(nb)], np.int32)
