@@ -990,6 +990,50 @@ int pesto_structalign(pesto_model* m, int32_t S, const int32_t* offsets, const f
                       int32_t* n_aligned_out, int32_t* n_ident_out, int32_t* dp_score_out, int32_t* unit_out, int32_t* round_out, float* tm_out,
                       double* rotation_out, double* translation_out, float* rmsd_out, double* history_out, int32_t ptr_kind, void* stream);
 
+/* ---- chain mapping of oligomers: which model chain lies on which reference chain ----
+ * Failures of the entry point below are reported through pesto_chainmap_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the TM-score group it uses the handle for its device, after
+ * pesto_synchronize(m), allocates its buffers stream-ordered per call, keeps no state between calls and synchronises `stream`.
+ * replaces: what the package lacked between its sequence matching and its scorers - the chain mapping step of OpenStructure's
+ * ChainMapper, of DockQ v2 and of MM-align / US-align, which pair the copies of an entity by structure before anything is scored. */
+const char* pesto_chainmap_last_error(void);
+
+enum {
+    PESTO_CHAINMAP_MAX_FRAMES = 1 << 23,      /* frames of one call */
+    PESTO_CHAINMAP_MAX_CHAINS = 64,           /* chains of a side */
+    PESTO_CHAINMAP_MAX_GROUP = 12,            /* chains of one group on a side: the assignment's table has 2^12 doubles */
+    PESTO_CHAINMAP_MAX_GROUPS = 128,          /* group ids lie in [0, 128) */
+    PESTO_CHAINMAP_MAX_LENGTH = 4096,         /* slots of a chain */
+    PESTO_CHAINMAP_MAX_ITER = 64,             /* n_iter */
+    PESTO_CHAINMAP_WORKSPACE = 1 << 28        /* bytes of gathered slot lists held at a time: it caps the shares of a frame's seeds, and the frames run in chunks */
+};
+
+/* replaces: one run of a chain mapper per decoy. xyz_ref float32 [Nr,3]: the reference's Cr chains back to back (ref_offsets int32
+ * [Cr + 1], ref_group int32 [Cr]); xyz float32 [F,Nm,3]: F models with the chain layout offsets int32 [Cm + 1], group int32 [Cm]. The
+ * four int32 arrays live where ptr_kind says, like the coordinates. All chains of a group, on both sides, have the same number of
+ * slots L_g (3 .. PESTO_CHAINMAP_MAX_LENGTH) and slot r is the same residue in each; a residue a chain lacks has NaN coordinates.
+ * norm_len, d0: positive (customarily the reference's finite residues and the TM-score d0 of that number).
+ * Definition, in double from the float32 inputs. Under a fit x' = (x - m) R + m_ref (pesto_fit.h, with its identity short cut) the pair
+ * sum of reference chain a and model chain b of one group is s(a, b) = sum_r 1 / (1 + (d_r / d0)^2) over the slots finite in both,
+ * d_r = |x'_{b,r} - y_{a,r}| scale. The assignment under a fit pairs, in every group, min(n_r, n_m) chains one to one so that the sum
+ * of s is the exact maximum (ties: the lowest set of chains used on the larger side, read as a bit mask; then, from the last chain of
+ * the smaller side backwards, the lowest chain of the larger side). total = the sum over the groups in ascending id.
+ * Seeds: seed a Cm + b for every pair (a, b) of one group with at least 3 common finite slots; its first fit is that of chain b onto
+ * chain a on those slots. A search makes up to n_iter fits: the assignment and total under the fit (the fit is visited); stop if the
+ * mapping equals that of the seed's previous fit; else fit all common slots of the mapped pairs together (fewer than 3: stop).
+ * Per frame f: score_out float32 = max total / norm_len over all visited fits; seed_out the lowest seed that attains it, round_out the
+ * first visit of that seed that does; mapping_out int32 [F,Cr] the model chain under every reference chain at that fit or -1;
+ * chain_score_out float32 [F,Cr] = s(a, mapping[a]) / (finite slots of a), 0 where unmapped; n_mapped_out int32; rotation_out double
+ * [F,3,3] and translation_out double [F,3]: x' = x R + t. A frame with an infinite coordinate (on either side) or without a seed: score
+ * and transform NaN, chain_score 0, mapping, seed and round -1, n_mapped 0.
+ * The scalar arguments are checked on the host; offsets and groups by a kernel before anything dereferences them: a refused call
+ * returns PESTO_ERR_INVALID and writes nothing. No atomics on the results: every output is bit-identical from call to call, between
+ * host and device pointers and between a frame alone and in a batch. */
+int pesto_chainmap(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr, int32_t Cm, const int32_t* ref_offsets, const int32_t* ref_group,
+                   const int32_t* offsets, const int32_t* group, const float* xyz_ref, const float* xyz, double norm_len, double d0, int32_t n_iter,
+                   double scale, float* score_out, int32_t* mapping_out, float* chain_score_out, int32_t* n_mapped_out, int32_t* seed_out,
+                   int32_t* round_out, double* rotation_out, double* translation_out, int32_t ptr_kind, void* stream);
+
 /* ---- essential dynamics of MD frames: fluctuations, covariance, cross-correlation, principal components (Amadei et al. 1993) ----
  * Failures of the entry points below are reported through pesto_dynamics_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the cluster group they use the handle for its device, after

@@ -18,6 +18,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "tmscore", "tm_score", "gdt", "tm_ca", "structure_tmscore",
            "sequences", "align_scores", "align_maps", "cluster_sequences", "split_clusters", "structure_sequences",
            "structalign", "align_structures", "tm_matrix", "ca_traces", "structure_align",
+           "chainmap", "chain_map", "apply_mapping", "structure_chainmap",
            "dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
@@ -83,6 +84,10 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         sa = importlib.import_module(".structalign", __name__)
         return sa if name == "structalign" else getattr(sa, name)
+    if name in ("chainmap", "chain_map", "apply_mapping", "structure_chainmap"):
+        import importlib
+        cm = importlib.import_module(".chainmap", __name__)
+        return cm if name == "chainmap" else getattr(cm, name)
     if name in ("dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA"):
         import importlib
         dy = importlib.import_module(".dynamics", __name__)

@@ -63,7 +63,7 @@ min(m, n) * 10000 < cov_bp * max(m, n) are not enumerated, because n_aligned <= 
 Neither changes labels. There is no k-mer or other inexact prefilter.
 
 Not built (structure-based alignment is structalign.py's): profile or multiple alignment, k-mer prefilters and database-scale search, nucleic
-acids, sequences above 4096, packed 16-bit arithmetic, chain permutation beyond the greedy pairing of match_atoms.
+acids, sequences above 4096, packed 16-bit arithmetic. (Chain permutation beyond the greedy pairing of match_atoms: chainmap.py.)
 
 Limits: 1 <= length <= MAX_LENGTH, A <= 32, gap_open <= 127, S <= 2**20, at most 2**31 - 1 pairs per call (2**20 for align_maps).
 """

@@ -48,9 +48,9 @@ tmscore.default_d0(Lmin), Q = 1024.
 No unit ever alive: tm 0, n_aligned 0, map -1, the identity transform, rmsd NaN, unit and round -1. A non-finite coordinate in either
 chain: NaN scores and transform, map -1, unit -1. Every output is bit-identical from call to call and between host and device inputs.
 
-Not built: secondary-structure initial alignments, TM-align's distance trimming before the final search, circular permutation, chain
-permutation of oligomers, multiple structure alignment, nucleic acids, a device-resident round loop (the host reads 8 bytes a unit once
-per round).
+Not built: secondary-structure initial alignments, TM-align's distance trimming before the final search, circular permutation, multiple
+structure alignment, nucleic acids, a device-resident round loop (the host reads 8 bytes a unit once per round). The chain permutation
+of an oligomer whose entities are known is chainmap.py's.
 
 Limits: 3 <= length <= MAX_LENGTH = 4096, P <= 2**20, rounds <= 64, 2 <= frag_starts <= 64, 0 <= gap_open <= 1. Every excess raises
 ValueError.

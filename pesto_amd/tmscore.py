@@ -44,8 +44,8 @@ and device inputs, and between a frame scored alone and in a batch.
 Ragged batch. sizes= (atom counts, as in lddt.py) lays B structures back to back in xyz_ref and xyz, one model each; sel is grouped by
 structure; L, d0 and the seeds are per structure (norm_len= and d0= take one value or B), and every output has one entry per structure.
 
-Not built: chain permutation of oligomers, MaxSub, mass weighting. (The correspondence is given here; structalign.py searches for it and
-has the pairwise TM matrix.)
+Not built: MaxSub, mass weighting. (The correspondence is given here; structalign.py searches for it and has the pairwise TM matrix;
+chainmap.py finds the chain permutation of an oligomer and puts the model's chains in the reference's order first.)
 
 Limits: 3 <= L <= MAX_LENGTH = 4096 per structure, F <= 2**23, N < 2**30, n_iter <= 1024. Every excess raises ValueError.
 """
