@@ -1034,6 +1034,63 @@ int pesto_chainmap(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr
                    double scale, float* score_out, int32_t* mapping_out, float* chain_score_out, int32_t* n_mapped_out, int32_t* seed_out,
                    int32_t* round_out, double* rotation_out, double* translation_out, int32_t ptr_kind, void* stream);
 
+/* ---- QS-score and interface contact score of assemblies, for a given chain mapping or for the mapping that maximises it ----
+ * Failures of the entry points below are reported through pesto_qsscore_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the chain mapping group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ * replaces: what the package lacked beside lDDT, TM-score and DockQ - the interface score of an assembly (QS-score, Bertoni et al. 2017,
+ * in the form OpenStructure states it; ICS as CASP's assembly category defines it) and the QS-optimal chain mapping that OpenStructure's
+ * ChainMapper searches for, one decoy per run.
+ *
+ * The layout is that of the chain mapping group (one point per residue, customarily CB, CA for glycine; all chains of a group share the
+ * slots of the group; a residue a chain lacks is NaN), with its limits PESTO_CHAINMAP_MAX_*; the four int32 layout arrays live where ptr_kind
+ * says, like the coordinates, as the chain mapping group takes them (device arrays, at most 65 ints each, are copied to the host on
+ * `stream` first: the job lists are made there and the layout is checked there). Definition, in double from the float32 inputs:
+ *     w(d) = 1 for d <= 5, exp(-2 ((d - 5) / 4.28)^2) for 5 < d < 12, 0 for d >= 12 (angstroms after scale)
+ *     a mapping m[a] = the model chain under reference chain a or -1, one to one, within groups; interface (a, a'), a < a', is mapped if
+ *     both are; a slot pair (r, s) of it is common if y[a,r], y[a',s], x[b,r], x[b',s] are finite (b = m[a], b' = m[a']);
+ *     d1 = |y[a,r] - y[a',s]| scale, d2 = |x[b,r] - x[b',s]| scale. Summed over the common slot pairs of a mapped interface:
+ *     num = w(min(d1,d2)) (1 - |d1 - d2| / 12) and shared = w(min(d1,d2)) where d1 < 12 and d2 < 12; extra = w of the one distance below
+ *     12 where exactly one is; mref = w(d1) where d1 < 12; mmdl = w(d2) where d2 < 12; n_shared = the pairs with d1 and d2 < contact_thr.
+ *     Wref (Wmdl[f]) = the sum of w over ALL chain pairs of the reference (of frame f) and their finite slot pairs; n_ref (n_model) = the
+ *     pairs among them below contact_thr.
+ *     qs_best = sum num / sum (shared + extra) over the mapped interfaces; qs_global = sum num / (sum (shared + extra) + (Wref - sum mref)
+ *     + (Wmdl - sum mmdl)); interface_qs[a,a'] = num / (shared + extra) of one mapped interface; a denominator that is not positive: NaN.
+ *     ics = 2 n_shared / (n_ref + n_model), precision = n_shared / n_model, recall = n_shared / n_ref; 0 / 0: NaN.
+ * Sums run in one order (a lane's slot pairs, the wave's butterfly, the waves, the blocks of 64 slots, the interfaces in ascending
+ * (a, a')); no atomics on results: every output is bit-identical from call to call, between host and device pointers and between a
+ * frame alone and in a batch. A frame with an infinite coordinate (on either side): NaN scores, counts -1 (mapping -1, n_mapped 0,
+ * index -1). */
+const char* pesto_qsscore_last_error(void);
+
+enum {
+    PESTO_QSSCORE_MAX_MAPPINGS = 1 << 20,     /* mappings pesto_qsmap enumerates: the product over the groups of max! / (max - min)! */
+    PESTO_QSSCORE_WORKSPACE = 1 << 28         /* bytes of chain-pair tables and block sums held at a time: the frames run in chunks */
+};
+
+/* replaces: one run of a QS-score scorer per decoy. mapping int32 [mapping_rows, Cr], mapping_rows 1 (one mapping for all frames) or F,
+ * lives where ptr_kind says and is checked by a kernel (model chains in [-1, Cm), each at most once, of the reference chain's group)
+ * whose verdict is read before anything is written. qs_best_out, qs_global_out, ics_out, precision_out, recall_out float32 [F], each
+ * rounded once; counts_out int32 [F,3] = n_ref, n_model, n_shared (exact; saturating at INT32_MAX); interface_qs_out float32 [F,Cr,Cr],
+ * symmetric, NaN on the diagonal and for interfaces that are not mapped. A refused call returns PESTO_ERR_INVALID and writes nothing. */
+int pesto_qsscore(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr, int32_t Cm, const int32_t* ref_offsets, const int32_t* ref_group,
+                  const int32_t* offsets, const int32_t* group, const float* xyz_ref, const float* xyz, const int32_t* mapping, int64_t mapping_rows,
+                  double contact_thr, double scale, float* qs_best_out, float* qs_global_out, float* ics_out, float* precision_out, float* recall_out,
+                  int32_t* counts_out, float* interface_qs_out, int32_t ptr_kind, void* stream);
+
+/* replaces: the search of a chain mapper for the QS-optimal mapping, one decoy per run. Every mapping that maps min(n_r, n_m) chains in
+ * every group present on both sides is scored from one table of chain-pair terms per frame; their number must not exceed
+ * PESTO_QSSCORE_MAX_MAPPINGS (PESTO_ERR_INVALID). mapping_out int32 [F,Cr] = the mapping of the largest qs_global (ties: the larger
+ * qs_best, then the lowest index), n_mapped_out int32 [F], index_out int64 [F] its number in the enumeration: a mixed-radix number over
+ * the groups present on both sides, the lowest group id the least significant digit; a group's digit is mixed-radix over the chains of
+ * its side with fewer chains (the reference's on a tie), the first the least significant, and the digit q of the k-th of them, in
+ * [0, max - k), picks the q-th still free chain of the other side in ascending order. The other outputs are those of pesto_qsscore for
+ * that mapping, bit for bit. A frame where no mapping has a qs_global: mapping -1, n_mapped 0, index -1. */
+int pesto_qsmap(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr, int32_t Cm, const int32_t* ref_offsets, const int32_t* ref_group,
+                const int32_t* offsets, const int32_t* group, const float* xyz_ref, const float* xyz, double contact_thr, double scale, int32_t* mapping_out,
+                int32_t* n_mapped_out, int64_t* index_out, float* qs_best_out, float* qs_global_out, float* ics_out, float* precision_out, float* recall_out,
+                int32_t* counts_out, float* interface_qs_out, int32_t ptr_kind, void* stream);
+
 /* ---- essential dynamics of MD frames: fluctuations, covariance, cross-correlation, principal components (Amadei et al. 1993) ----
  * Failures of the entry points below are reported through pesto_dynamics_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the cluster group they use the handle for its device, after

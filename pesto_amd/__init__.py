@@ -19,6 +19,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "sequences", "align_scores", "align_maps", "cluster_sequences", "split_clusters", "structure_sequences",
            "structalign", "align_structures", "tm_matrix", "ca_traces", "structure_align",
            "chainmap", "chain_map", "apply_mapping", "structure_chainmap",
+           "qsscore", "qs_score", "qs_map", "n_mappings", "mapping_of_index", "interface_points", "structure_qsscore",
            "dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
@@ -88,6 +89,10 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         cm = importlib.import_module(".chainmap", __name__)
         return cm if name == "chainmap" else getattr(cm, name)
+    if name in ("qsscore", "qs_score", "qs_map", "n_mappings", "mapping_of_index", "interface_points", "structure_qsscore"):
+        import importlib
+        qs = importlib.import_module(".qsscore", __name__)
+        return qs if name == "qsscore" else getattr(qs, name)
     if name in ("dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA"):
         import importlib
         dy = importlib.import_module(".dynamics", __name__)

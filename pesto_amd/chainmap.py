@@ -43,9 +43,9 @@ A frame with an infinite coordinate, or without any seed, gets score NaN, a NaN 
 coordinate in the reference raises ValueError. Every output is bit-identical from call to call, between host and device inputs, and
 between a frame scored alone and in a batch.
 
-Not built: groups of more than 12 chains (24-mers, capsids: they need a Hungarian or greedy assignment); interface-based objectives
-(QS-score); sequence-free mapping of chains whose entity is unknown (structalign.py aligns such chains); more than one point per
-residue.
+Not built: groups of more than 12 chains (24-mers, capsids: they need a Hungarian or greedy assignment); sequence-free mapping of
+chains whose entity is unknown (structalign.py aligns such chains); more than one point per residue. (The interface-based objective,
+QS-score, and the mapping that maximises it: qsscore.py.)
 
 Limits: at most MAX_GROUP = 12 chains of a group and MAX_CHAINS = 64 chains per side, 3 <= L_g <= MAX_LENGTH = 4096, F <= 2**23,
 Nr, Nm < 2**30, 1 <= n_iter <= MAX_ITER = 64. Every excess raises ValueError before any launch.
@@ -198,7 +198,6 @@ def structure_chainmap(reference, predicted, min_identity=0.9, model=None, **kw)
     sequences.match_atoms' five results with the residues paired by the slots under the found mapping: lddt.lddt, tmscore.tm_score and
     dockq take it directly."""
     from .lddt import _structure_dict
-    from .sequences import _matched, align_maps, cluster_sequences
     from .structalign import ca_traces
     if "scale" in kw:
         raise ValueError("structure_chainmap works in angstroms: scale is not taken")
@@ -206,6 +205,22 @@ def structure_chainmap(reference, predicted, min_identity=0.9, model=None, **kw)
     ta, tb = ca_traces(a), ca_traces(b)
     if not ta or not tb:
         raise ValueError("each structure needs a protein chain")
+    kept_a, kept_b, side_arrays, result_of = _entity_slots(a, b, ta, tb, min_identity, model)
+    ya, ro, rg = side_arrays(kept_a, ta, 0)
+    xb, mo, mg = side_arrays(kept_b, tb, len(ta))
+    out = chain_map(ya, ro, rg, xb[None], mo, mg, scale=1.0, model=model, **kw)
+    chains, match = result_of(np.asarray(_lib.host(out.mapping))[0])
+    return out, chains, match
+
+
+def _entity_slots(a, b, ta, tb, min_identity, model):
+    """The entities and slots of two structure dicts a (the reference) and b, as structure_chainmap states them, from their per-chain
+    traces ta and tb (structalign.ca_traces, or any list of the same residues such as qsscore.interface_points). Returns (kept_a, kept_b,
+    side_arrays, result_of): the chains of either side that belong to a kept entity (indices into ta and tb); side_arrays(chains,
+    traces, base) -> (xyz float32 [N, 3] with NaN where a chain lacks a slot, offsets int32, group int64) of one side's kept chains
+    (base 0 for the reference, len(ta) for the model) with the points of ``traces``; result_of(mapping) -> (chains, match) of a
+    mapping over the kept chains: the names of the mapped pairs and sequences.match_atoms' five results."""
+    from .sequences import _matched, align_maps, cluster_sequences
     na = len(ta)
     seqs = [t[2] for t in ta + tb]
     labels = np.asarray(_lib.host(cluster_sequences(seqs, min_identity=min_identity, model=model))).astype(np.int64)
@@ -267,23 +282,22 @@ def structure_chainmap(reference, predicted, min_identity=0.9, model=None, **kw)
             s = slots[base + c]
             xyz[offs[k] + s[s >= 0]] = traces[c][1][s >= 0]
         return xyz, offs, np.array([labels[base + c] for c in chains], np.int64)
-    ya, ro, rg = side_arrays(kept_a, ta, 0)
-    xb, mo, mg = side_arrays(kept_b, tb, na)
-    out = chain_map(ya, ro, rg, xb[None], mo, mg, scale=1.0, model=model, **kw)
-    mapping = np.asarray(_lib.host(out.mapping))[0]
-    mapped = [(kept_a[k], kept_b[int(j)]) for k, j in enumerate(mapping) if j >= 0]
 
-    def partner_of(da, db, fa, fb):
-        row_a = {int(f): r for r, f in enumerate(fa)}
-        row_b = {int(f): r for r, f in enumerate(fb)}
-        partner = np.full(fa.size, -1, np.int64)
-        for i, j in mapped:
-            sa, sb = slots[i], slots[na + j]
-            of_slot = {int(s): q for q, s in enumerate(sb) if s >= 0}
-            for r, s in enumerate(sa):
-                q = of_slot.get(int(s), -1) if s >= 0 else -1
-                if q >= 0:
-                    partner[row_a[int(ta[i][3][r])]] = row_b[int(tb[j][3][q])]
-        return partner
-    match = _matched(a, b, model, partner_of)[:5]
-    return out, [(ta[i][0], tb[j][0]) for i, j in mapped], match
+    def result_of(mapping):
+        mapped = [(kept_a[k], kept_b[int(j)]) for k, j in enumerate(mapping) if j >= 0]
+
+        def partner_of(da, db, fa, fb):
+            row_a = {int(f): r for r, f in enumerate(fa)}
+            row_b = {int(f): r for r, f in enumerate(fb)}
+            partner = np.full(fa.size, -1, np.int64)
+            for i, j in mapped:
+                sa, sb = slots[i], slots[na + j]
+                of_slot = {int(s): q for q, s in enumerate(sb) if s >= 0}
+                for r, s in enumerate(sa):
+                    q = of_slot.get(int(s), -1) if s >= 0 else -1
+                    if q >= 0:
+                        partner[row_a[int(ta[i][3][r])]] = row_b[int(tb[j][3][q])]
+            return partner
+        match = _matched(a, b, model, partner_of)[:5]
+        return [(ta[i][0], tb[j][0]) for i, j in mapped], match
+    return kept_a, kept_b, side_arrays, result_of

@@ -37,7 +37,8 @@ fl32(scale), and a NaN distance passes no test.
                    2 (medium)      10 preserved >= 3 P   and (lrmsd <= 5  or irmsd <= 2)
                    1 (acceptable)  10 preserved >= P     and (lrmsd <= 10 or irmsd <= 4)
                    0               otherwise
-Every output is bit-identical from call to call and between host and device inputs.
+Every output is bit-identical from call to call and between host and device inputs. (DockQ scores ONE receptor-ligand pair; the
+interface score of a whole assembly, over all its chain pairs and with its chain mapping, is qsscore.py's QS-score.)
 
 Limits: F <= 2**23, N < 2**30 (docking.py's); P <= MAX_PAIRS = 2**24 native pairs, each with fewer than 2**31 atom pairs; the
 selections hold distinct atoms, so at most N each; the set-up goes through frame_contacts at one frame, so |ids_R| * |ids_L| < 2**31.

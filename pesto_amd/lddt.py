@@ -30,7 +30,8 @@ root, no contraction. A NaN distance passes no test.
     residue[f,r]     float32(double(sum_k preserved[f, r, k]) / double(T * total[r])). It is NaN where total[r] == 0.
     score[f]         the same quotient over the int64 sums over the residues. It is NaN when K == 0.
 Both tests are strict. This is our definition; no equality with OpenStructure's lddt is claimed. Not reproduced: the stereochemistry
-filter, the renaming of symmetric side-chain atoms (ASP OD1/OD2 and the like), a sequence separation, periodic images.
+filter, the renaming of symmetric side-chain atoms (ASP OD1/OD2 and the like), a sequence separation, periodic images. (The contact-based
+interface score of an assembly, QS-score with ICS, which is reported next to lDDT: qsscore.py.)
 Every output is bit-identical from call to call, and between host and device inputs.
 
 Ragged batch. sizes= (atom counts, as in sasa.py) lays B structures back to back in xyz_ref and xyz, one model each: an AlphaFold model
