@@ -1150,6 +1150,85 @@ int pesto_pca(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* 
 int pesto_project(pesto_model* m, int64_t F, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, int32_t k, const float* mean,
                   const double* components, double scale, float* proj_out, int32_t ptr_kind, void* stream);
 
+/* ---- elastic-network normal modes of one structure: ANM (Atilgan et al. 2001) and GNM (Bahar et al. 1997) ----
+ * Failures of the entry points below are reported through pesto_enm_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the dynamics group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`.
+ *
+ * Definition (this library's own; no equality with another package is claimed). xyz float32 [N,3]; sel int32 [n_sel] node indices in
+ * [0, N) or NULL for all (n_sel = N); an index outside the range or a non-finite selected coordinate refuses the call on the device's
+ * verdict (PESTO_ERR_INVALID) before any output is written. The springs are the ordered pairs (i, j), i != j, of selected nodes with
+ *     fl32(sqrt_rn((dx*dx + dy*dy) + dz*dz)) * fl32(scale) < fl32(cutoff)   (strict; the distance of the lDDT group)   and dist2 > 0
+ * with the stiffness k_ij = gamma |r|^-p, r = scale ((double)x_j - (double)x_i), p 0 or 2, gamma > 0 and finite, cutoff and scale
+ * positive float32 values. dim = 3 (ANM): the Hessian, double [3 n_sel, 3 n_sel], H_ij = -k_ij r r^T / |r|^2 for a spring, H_ii =
+ * -sum_j H_ij in ascending j. dim = 1 (GNM): the Kirchhoff matrix, Gamma_ij = -k_ij, Gamma_ii = sum_j k_ij. b = 2 max_i sum_j k_ij
+ * bounds both spectra (Gershgorin for Gamma; H <= Gamma (x) I_3 because u u^T <= I for every spring). Every sum runs in an order fixed
+ * by the shapes and the list alone (no floating-point atomics): every output is bit-identical from call to call. */
+const char* pesto_enm_last_error(void);
+
+enum {
+    PESTO_ENM_MAX_NODES = 1 << 24,            /* N; also the frames of pesto_enm_deform */
+    PESTO_ENM_MAX_SPRINGS = 1 << 27,          /* list entries (ordered pairs) of one call */
+    PESTO_ENM_MAX_DENSE = 1 << 27,            /* (dim n_sel)^2 of pesto_enm_matrix, n^2 of the correlation: 1 GiB of doubles */
+    PESTO_ENM_MAX_MODES = 32                  /* n_modes of pesto_enm_modes: half the solver's block of 64 vectors */
+};
+
+/* The spring list as a CSR over the selected nodes in the selection's numbering: offsets_out int64 [n_sel + 1]; j_out int32 and k_out
+ * float64 [capacity], row i = offsets[i] .. offsets[i + 1] holds node i's partners j ascending with k_ij. n_springs_out (one int64 in
+ * HOST memory) = K, the list's entries (every spring twice); bound_out (one double in HOST memory) = b. j_out and k_out are filled
+ * where K <= capacity (0 <= capacity <= PESTO_ENM_MAX_SPRINGS; with 0 they may be NULL): call once for K, once more with room for it.
+ * The cell grid of the contact searches at cutoff / scale, a count pass, the 64-bit scan and a fill pass; a wave per row sorts it by
+ * ranking every entry against the whole row: d^2 / 64 comparisons a wave for a row of d entries, milliseconds for a protein's rows of
+ * some hundred, but quadratic: a dense cloud whose rows hold about n entries costs n^3 / 64 in all and is not what the limits promise
+ * to be quick. R of the modes call is orthonormalised by ONE workgroup in some 40 reductions over the 3 n_sel coordinates: linear in
+ * n_sel, about a millisecond per 10^5 nodes a reduction, so seconds near PESTO_ENM_MAX_NODES. */
+int pesto_enm_network(pesto_model* m, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, double cutoff, double scale, double gamma, int32_t p,
+                      int64_t capacity, int64_t* offsets_out, int32_t* j_out, double* k_out, int64_t* n_springs_out, double* bound_out, int32_t ptr_kind,
+                      void* stream);
+
+/* out float64 [dim n_sel, dim n_sel]: the Hessian (dim 3) or the Kirchhoff matrix (dim 1), cleared and filled from the list; bitwise
+ * symmetric, every diagonal 3 x 3 block included. (dim n_sel)^2 <= PESTO_ENM_MAX_DENSE. */
+int pesto_enm_matrix(pesto_model* m, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, double cutoff, double scale, double gamma, int32_t p,
+                     int32_t dim, double* out, int32_t ptr_kind, void* stream);
+
+/* The k = n_modes lowest eigenpairs of the Hessian (dim 3, n_sel >= 3, k <= min(PESTO_ENM_MAX_MODES, 3 n_sel - 6)) or of the Kirchhoff
+ * matrix (dim 1, n_sel >= 2, k <= min(PESTO_ENM_MAX_MODES, n_sel - 1)) restricted to the complement of R, the rigid-body basis: three
+ * translations and three rotations about the centroid, orthonormalised in double with null directions dropped (dim 1: the constant
+ * vector). Matrix-free: the operator walks the list, one wave per node with the 64 vectors of the block across its lanes. Solver:
+ * Chebyshev-filtered subspace iteration (Zhou and Saad 2007) on min(64, dim n_sel - rank R) vectors with Rayleigh-Ritz through the
+ * 64 x 64 one-sided Jacobi and the Gram orthonormalisation of the dynamics group; the filter damps [largest Ritz value of the block, b],
+ * is scaled against the lowest Ritz value, and has the degree (at most 4096) that gains 1e3 on the k-th mode; the rigid motions are
+ * projected out of every product and once after every filter. A block that spans the whole complement needs one Rayleigh-Ritz step and
+ * no filter. At most max_iter >= 1 Rayleigh-Ritz steps; the host reads the Ritz values after each.
+ *     eig_out float64 [k]: ascending; a Ritz value <= 1e-10 b is a floppy direction and is reported as exactly 0 (its mode is kept)
+ *     modes_out float64 [k, n_sel, dim]: orthonormal rows; in each the entry of largest magnitude is positive (the lowest index on ties)
+ *     resid_out float64 [k] = |(I - R R^T) H v_i - theta_i v_i|_2 as the iteration measures it
+ *     bound_out: one double in HOST memory, b;   n_springs_out: one int64 in HOST memory, K
+ *     info_out int32 [6] in HOST memory: n_zero (the floppy directions among the k), iterations, converged, applies (operator
+ *         applications on the block), the most sweeps any of the call's Jacobi runs took, rank R
+ * converged = (max_i resid_i <= tol b), tol >= 0; it is reported, never an error. */
+int pesto_enm_modes(pesto_model* m, int64_t N, int64_t n_sel, const float* xyz, const int32_t* sel, double cutoff, double scale, double gamma, int32_t p,
+                    int32_t dim, int32_t n_modes, double tol, int32_t max_iter, double* eig_out, double* modes_out, double* resid_out, double* bound_out,
+                    int64_t* n_springs_out, int32_t* info_out, int32_t ptr_kind, void* stream);
+
+/* From k modes (eig float64 [k], modes float64 [k, n, dim], 1 <= k <= 64), the sums running over eig_k > 0 in ascending k:
+ *     fluct_out float64 [n] = factor sum_k |v_k,i|^2 / eig_k                                              (NULL: not wanted)
+ *     corr_out float32 [n, n] = C_ij / sqrt(C_ii C_jj), C_ij = sum_k (v_k,i . v_k,j) / eig_k, rounded once; bitwise symmetric, exactly 1
+ *         on the diagonal, 0 (never NaN) for a node without fluctuation; n^2 <= PESTO_ENM_MAX_DENSE        (NULL: not wanted) */
+int pesto_enm_fluctuations(pesto_model* m, int64_t k, int64_t n, int32_t dim, const double* eig, const double* modes, double factor, double* fluct_out,
+                           float* corr_out, int32_t ptr_kind, void* stream);
+
+/* overlap_out float64 [ka, kb] = |a_i . b_j| for modes_a float64 [ka, len] and modes_b float64 [kb, len], 1 <= ka, kb <= 64; with
+ * normalise_b every b_j is divided by its length first (a displacement between two conformers; a zero one gives 0). */
+int pesto_enm_overlap(pesto_model* m, int64_t ka, int64_t kb, int64_t len, const double* modes_a, const double* modes_b, int32_t normalise_b,
+                      double* overlap_out, int32_t ptr_kind, void* stream);
+
+/* xyz_out float32 [F, N, 3] = fl32((double)x_a + sum_k A[f,k] v_k[node_of_atom[a]]), the sum in ascending k, in double, rounded once:
+ * xyz float32 [N,3], modes float64 [k, n, 3] (1 <= k <= 64), amplitudes float64 [F, k], node_of_atom int32 [N] with values in [0, n)
+ * (checked on the device before anything is written) or NULL with n = N: atoms are nodes. F N 3 <= 2^36. */
+int pesto_enm_deform(pesto_model* m, int64_t F, int64_t N, int64_t n, int64_t k, const float* xyz, const double* modes, const double* amplitudes,
+                     const int32_t* node_of_atom, float* xyz_out, int32_t ptr_kind, void* stream);
+
 /* ---- hydrogen bonds and periodic unwrapping (hydrogen_bonds and unwrap_pbc of md_analysis/mdtraj_utils/trajectory_utils.py) ----
  * Failures of the entry points below are reported through pesto_hbonds_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after

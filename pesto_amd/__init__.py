@@ -21,6 +21,8 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "chainmap", "chain_map", "apply_mapping", "structure_chainmap",
            "qsscore", "qs_score", "qs_map", "n_mappings", "mapping_of_index", "interface_points", "structure_qsscore",
            "dynamics", "fluctuations", "rmsf", "covariance", "cross_correlation", "pca", "project", "PCA",
+           "normalmodes", "network", "hessian", "kirchhoff", "anm", "gnm", "Modes", "mode_fluctuations", "mode_correlation", "overlap",
+           "cumulative_overlap", "deform", "sample_amplitudes", "mode_path", "structure_modes",
            "CONFIGS", "config_model", "config_i_v4_1", "config_i_v4_0", "config_i_v3_0", "config_i_v3_1"]
 
 
@@ -97,4 +99,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         dy = importlib.import_module(".dynamics", __name__)
         return dy if name == "dynamics" else getattr(dy, name)
+    if name in ("normalmodes", "network", "hessian", "kirchhoff", "anm", "gnm", "Modes", "mode_fluctuations", "mode_correlation", "overlap",
+                "cumulative_overlap", "deform", "sample_amplitudes", "mode_path", "structure_modes"):
+        import importlib
+        nm = importlib.import_module(".normalmodes", __name__)
+        return nm if name == "normalmodes" else getattr(nm, name)
     raise AttributeError(name)

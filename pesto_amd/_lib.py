@@ -82,6 +82,8 @@ ABI_SYMBOLS = [
     "pesto_chainmap_last_error", "pesto_chainmap",
     "pesto_qsscore_last_error", "pesto_qsscore", "pesto_qsmap",
     "pesto_dynamics_last_error", "pesto_fluctuations", "pesto_covariance", "pesto_cross_correlation", "pesto_pca", "pesto_project",
+    "pesto_enm_last_error", "pesto_enm_network", "pesto_enm_matrix", "pesto_enm_modes", "pesto_enm_fluctuations", "pesto_enm_overlap",
+    "pesto_enm_deform",
     "pesto_rank_last_error", "pesto_rank_scores", "pesto_rank_curves", "pesto_rank_histogram",
     "pesto_surface_last_error", "pesto_surface_nearest", "pesto_surface_areas", "pesto_surface_residues", "pesto_surface_vertex_scores",
     "pesto_surface_scored",
@@ -221,6 +223,16 @@ def load():
     lib.pesto_pca.argtypes = [c_p, i64, i64, i64, c_p, c_p, i32, ctypes.c_double, i32, ctypes.c_double, i32, c_p, c_p, c_p, c_p, c_p,
                               P(ctypes.c_double), P(i32), i32, c_p]
     lib.pesto_project.argtypes = [c_p, i64, i64, i64, c_p, c_p, i32, c_p, c_p, ctypes.c_double, c_p, i32, c_p]
+    lib.pesto_enm_last_error.restype = ctypes.c_char_p
+    lib.pesto_enm_last_error.argtypes = []
+    lib.pesto_enm_network.argtypes = [c_p, i64, i64, c_p, c_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, i64, c_p, c_p, c_p, P(i64),
+                                      P(ctypes.c_double), i32, c_p]
+    lib.pesto_enm_matrix.argtypes = [c_p, i64, i64, c_p, c_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, i32, c_p, i32, c_p]
+    lib.pesto_enm_modes.argtypes = [c_p, i64, i64, c_p, c_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, i32, i32, ctypes.c_double, i32,
+                                    c_p, c_p, c_p, P(ctypes.c_double), P(i64), P(i32), i32, c_p]
+    lib.pesto_enm_fluctuations.argtypes = [c_p, i64, i64, i32, c_p, c_p, ctypes.c_double, c_p, c_p, i32, c_p]
+    lib.pesto_enm_overlap.argtypes = [c_p, i64, i64, i64, c_p, c_p, i32, c_p, i32, c_p]
+    lib.pesto_enm_deform.argtypes = [c_p, i64, i64, i64, i64, c_p, c_p, c_p, c_p, c_p, i32, c_p]
     lib.pesto_hbonds_last_error.restype = ctypes.c_char_p
     lib.pesto_hbonds_last_error.argtypes = []
     lib.pesto_frame_hbonds.argtypes = [c_p, i64, i64, i64, i64, c_p, c_p, c_p, c_p, ctypes.c_float, ctypes.c_float, ctypes.c_double, i64, c_p, c_p,
@@ -276,17 +288,17 @@ def load():
                         "pesto_hbonds_last_error", "pesto_cluster_last_error", "pesto_peaks_last_error", "pesto_rank_last_error", "pesto_surface_last_error",
                         "pesto_train_last_error", "pesto_dockq_last_error", "pesto_lddt_last_error", "pesto_tmscore_last_error",
                         "pesto_dynamics_last_error", "pesto_align_last_error", "pesto_structalign_last_error", "pesto_chainmap_last_error",
-                        "pesto_qsscore_last_error"):
+                        "pesto_qsscore_last_error", "pesto_enm_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are twenty-two channels:
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are twenty-three channels:
     pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
     pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error, pesto_docking_last_error,
-    pesto_hbonds_last_error, pesto_cluster_last_error, pesto_peaks_last_error, pesto_dockq_last_error, pesto_lddt_last_error, pesto_tmscore_last_error, pesto_align_last_error, pesto_structalign_last_error, pesto_chainmap_last_error, pesto_qsscore_last_error, pesto_dynamics_last_error, pesto_rank_last_error, pesto_surface_last_error and pesto_train_last_error."""
+    pesto_hbonds_last_error, pesto_cluster_last_error, pesto_peaks_last_error, pesto_dockq_last_error, pesto_lddt_last_error, pesto_tmscore_last_error, pesto_align_last_error, pesto_structalign_last_error, pesto_chainmap_last_error, pesto_qsscore_last_error, pesto_dynamics_last_error, pesto_enm_last_error, pesto_rank_last_error, pesto_surface_last_error and pesto_train_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")
