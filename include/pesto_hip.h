@@ -775,6 +775,76 @@ int pesto_dockq(pesto_model* m, int64_t F, int64_t N, const float* xyz_ref, cons
 int pesto_fit_rmsd(pesto_model* m, int64_t F, int64_t F_ref, int64_t N, const float* xyz_ref, const float* xyz, int64_t n_fit, const int32_t* sel_fit,
                    int64_t n_measure, const int32_t* sel_measure, double scale, float* rmsd_out, int32_t ptr_kind, void* stream);
 
+/* ---- rigid poses of a ligand on a receptor: scoring against the predicted interfaces, sliding to contact, ranking ----
+ * Failures of the entry points below are reported through pesto_poses_last_error() (thread-local message of the last failing call of
+ * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after
+ * pesto_synchronize(m), allocate their buffers stream-ordered per call, keep no state between calls and synchronise `stream`. The
+ * definitions are this library's own. Pose f is (R_f = rotations[f] float32 [3,3] row-major, t_f = translations[f] float32 [3]), both
+ * finite; R_f need not be orthonormal. Ligand atom x has, in pose f, the coordinates
+ *     y_a = ((R[a,0]*x_0 + R[a,1]*x_1) + R[a,2]*x_2) + t_a        float32, every operation rounded as written, no contraction
+ * and every function sees the ligand through this placement alone. The distance and its test are the docking group's: d =
+ * fl32(sqrt_rn((dx*dx + dy*dy) + dz*dz)) * scale < r, a NaN distance passes no test. No floating-point atomics: every output is
+ * bit-identical from call to call, between host and device pointers, and for a pose alone or inside a batch. Every index is checked
+ * for its range, and every probability, pose and direction for its value, on the device before anything relies on it; a refused call
+ * returns PESTO_ERR_INVALID and writes nothing. Coordinates may hold anything: a non-finite one gives its atom no pair. */
+const char* pesto_poses_last_error(void);
+
+enum {
+    PESTO_POSES_MAX_FRAMES = 1 << 23,         /* a workgroup of 256 threads per pose, below 2^32 threads per launch */
+    PESTO_POSES_MAX_RESIDUES = 4096,          /* residues of either side: a residue mask is at most 128 words of LDS */
+    PESTO_POSES_MAX_PAIRS = 0x7fffffff,       /* N_R * N_L: a pose's contact count is an int32 */
+    PESTO_POSES_MAX_PLACED = 0x7fffffff       /* F * (N_R + N_L) atoms written by pesto_poses_materialize */
+};
+
+/* how well each of F poses agrees with the two predicted interfaces. xyz_R float32 [N_R,3] (never moved), xyz_L float32 [N_L,3];
+ * res_R int32 [N_R]: the residue row of every receptor atom, in [0, R_R); the ligand's atoms come ordered by residue: perm_L int32 [N_L]
+ * (atom indices in [0, N_L); that they are distinct, a permutation, is the caller's contract and is NOT checked: an index named twice
+ * is counted twice, nothing else) and off_L int32 [R_L + 1] (0 = off_L[0] < ... < off_L[R_L] = N_L: residue s owns
+ * perm_L[off_L[s] .. off_L[s+1])); 1 <= R_R, R_L <= PESTO_POSES_MAX_RESIDUES; p_R float32 [R_R], p_L float32 [R_L]: the predicted interface
+ * probability of every residue, finite and >= 0; 0 <= r_clash <= r_contact, scale > 0; N_R * N_L <= PESTO_POSES_MAX_PAIRS. Per pose f:
+ *     n_contact_out int32 [F]: the atom pairs (receptor atom, placed ligand atom) with d < r_contact; n_clash_out: with d < r_clash
+ *     n_res_R_out, n_res_L_out int32 [F]: the residues of either side with a contact pair, the pose's interfaces I_R, I_L
+ *     n_pairs_out int32 [F]: the distinct residue pairs (r, s) with a contact pair, C
+ *     w_R_out, w_L_out double [F] = sum over I_R of p_R[r], sum over I_L of p_L[s]; w_pair_out double [F] = sum over C of
+ *         double(p_R[r]) * double(p_L[s]) (every product exact), each in double in an order that depends on the pose's sets alone
+ *     score_out float32 [F] = float32((dice_R + dice_L) / 2), dice_R = 2 w_R / (n_res_R + P_R), P_R = sum of p_R in double, 0 where the
+ *         denominator is 0; dice_L likewise: the soft Dice overlap of the predicted and the posed interface
+ *     masks_out uint32 [F, ceil(R_R / 32) + ceil(R_L / 32)] or NULL: bit r % 32 of word r / 32 set for r in I_R, then the ligand's words
+ * One cell grid over the receptor per call, one workgroup per pose, a wave per ligand residue; the frames are never stored and no pair
+ * list is written. A receptor atom with a non-finite coordinate has no pair by the definition (its distances are NaN or infinite); the
+ * grid is built on a copy in which such atoms sit on the first finite atom (the origin without one), and they are tested as NaN. */
+int pesto_poses_scores(pesto_model* m, int64_t F, int64_t N_R, int64_t N_L, int32_t R_R, int32_t R_L, const float* xyz_R, const float* xyz_L,
+                       const int32_t* res_R, const int32_t* perm_L, const int32_t* off_L, const float* rotations, const float* translations,
+                       const float* p_R, const float* p_L, float r_contact, float r_clash, float scale, int32_t* n_contact_out, int32_t* n_clash_out,
+                       int32_t* n_res_R_out, int32_t* n_res_L_out, int32_t* n_pairs_out, double* w_R_out, double* w_L_out, double* w_pair_out,
+                       float* score_out, uint32_t* masks_out, int32_t ptr_kind, void* stream);
+
+/* how far the ligand, placed with t = origins[f] and withdrawn along +u = directions[f] (float32 [F,3], used as given,
+ * | |u|^2 - 1 | <= 1e-3 in double), can be pushed back until it first touches the receptor. In double, every operation rounded as
+ * written, over every atom pair (i of the receptor, j of the ligand):
+ *     w = double(y_j) - double(x_i);  b = (w0*u0 + w1*u1) + w2*u2;  c = ((w0*w0 + w1*w1) + w2*w2) - b*b
+ *     rho = double(r_touch) / double(scale);  disc = rho*rho - c;  the pair counts where disc > 0;  s_ij = -b + sqrt(disc)
+ * s_out double [F] = the maximum of s_ij; pair_out int32 [F,2] = the (i, j) that attains it, the smallest (i, then j) among ties;
+ * translations_out float32 [F,3] = float32(double(origin) + s * u) per component. Where no pair counts (the ray misses; a non-finite
+ * w counts for nothing): s and the translation are NaN and the pair is (-1, -1). r_touch >= 0, scale > 0, N_R * N_L <=
+ * PESTO_POSES_MAX_PAIRS. All pairs, one workgroup per pose, receptor tiles in LDS; the maximum does not depend on the order. */
+int pesto_poses_slide(pesto_model* m, int64_t F, int64_t N_R, int64_t N_L, const float* xyz_R, const float* xyz_L, const float* rotations,
+                      const float* origins, const float* directions, float r_touch, float scale, double* s_out, float* translations_out,
+                      int32_t* pair_out, int32_t ptr_kind, void* stream);
+
+/* the placed frames, for the entry points that take frames: xyz_out float32 [F, N_R + N_L, 3], the receptor's rows first (copied;
+ * N_R = 0 and xyz_R = NULL: the ligand alone), then the placement of every ligand atom, bit for bit. F * (N_R + N_L) <=
+ * PESTO_POSES_MAX_PLACED. */
+int pesto_poses_materialize(pesto_model* m, int64_t F, int64_t N_R, int64_t N_L, const float* xyz_R, const float* xyz_L, const float* rotations,
+                            const float* translations, float* xyz_out, int32_t ptr_kind, void* stream);
+
+/* the best poses: index_out int32 [min(k, F)], of which the first count_out[0] = min(k, eligible) are written (count_out: HOST int64
+ * [1]). Eligible are the poses whose score float32 [F] is not a NaN and, with n_clash int32 [F] given (NULL: no filter), n_clash <=
+ * max_clash; they come by score descending (-0.0 equals 0.0), ties by index ascending. k >= 0. One stable radix sort of 64-bit keys on
+ * the score's 32 bits; no host sort. */
+int pesto_poses_top(pesto_model* m, int64_t F, int64_t k, const float* score, const int32_t* n_clash, int32_t max_clash, int32_t* index_out,
+                    int64_t* count_out, int32_t ptr_kind, void* stream);
+
 /* ---- lDDT model-quality scoring (Mariani et al. 2013): superposition-free, per residue, over all frames ----
  * Failures of the entry points below are reported through pesto_lddt_last_error() (thread-local message of the last failing call of
  * this group; an invalid handle's message is copied there too). Like the docking group they use the handle for its device, after

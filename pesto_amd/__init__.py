@@ -14,6 +14,7 @@ __all__ = ["Model", "evaluate", "interface_labels", "bc_scoring", "benchmark_ass
            "clustering", "pairwise_rmsd", "gromos_clusters", "cluster_frames",
            "peaks", "interface_centers", "weighted_centers", "distance_quantile", "density_peaks", "cluster_interface_frames",
            "dockq", "lrmsd", "fit_rmsd", "native_pairs", "capri_class",
+           "poses", "pose_scores", "slide_to_contact", "materialize", "top_poses", "rotation_set", "poses_about", "guided_dock", "PoseScores",
            "lddt", "ilddt", "lddt_ca", "reference_pairs", "structure_lddt",
            "tmscore", "tm_score", "gdt", "tm_ca", "structure_tmscore",
            "sequences", "align_scores", "align_maps", "cluster_sequences", "split_clusters", "structure_sequences",
@@ -71,7 +72,11 @@ def __getattr__(name):  # lazy: importing the package must not need torch or the
         import importlib
         dq = importlib.import_module(".dockq", __name__)
         return dq if name == "dockq" else getattr(dq, name)
-    if name in ("lddt", "ilddt", "lddt_ca", "reference_pairs", "structure_lddt"):      # (lddt: the module; its function is lddt.lddt)
+    if name in ("poses", "pose_scores", "slide_to_contact", "materialize", "top_poses", "rotation_set", "poses_about", "guided_dock", "PoseScores"):
+        import importlib
+        ps = importlib.import_module(".poses", __name__)
+        return ps if name == "poses" else getattr(ps, name)
+    if name in ("lddt", "ilddt", "lddt_ca", "reference_pairs", "structure_lddt"):     # (lddt: the module; its function is lddt.lddt)
         import importlib
         ld = importlib.import_module(".lddt", __name__)
         return ld if name == "lddt" else getattr(ld, name)

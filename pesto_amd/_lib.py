@@ -75,6 +75,7 @@ ABI_SYMBOLS = [
     "pesto_cluster_last_error", "pesto_pairwise_rmsd", "pesto_gromos_clusters",
     "pesto_peaks_last_error", "pesto_weighted_centers", "pesto_pair_distance_rank", "pesto_density_peaks",
     "pesto_dockq_last_error", "pesto_dockq", "pesto_fit_rmsd",
+    "pesto_poses_last_error", "pesto_poses_scores", "pesto_poses_slide", "pesto_poses_materialize", "pesto_poses_top",
     "pesto_lddt_last_error", "pesto_lddt_pairs", "pesto_lddt",
     "pesto_tmscore_last_error", "pesto_tmscore",
     "pesto_align_last_error", "pesto_align_scores", "pesto_align_maps",
@@ -188,6 +189,13 @@ def load():
     lib.pesto_dockq.argtypes = [c_p, i64, i64, c_p, c_p, i64, c_p, i64, c_p, i64, c_p, i64, c_p, i64, c_p, ctypes.c_float, ctypes.c_double, c_p, c_p, c_p,
                                 c_p, c_p, c_p, i32, c_p]
     lib.pesto_fit_rmsd.argtypes = [c_p, i64, i64, i64, c_p, c_p, i64, c_p, i64, c_p, ctypes.c_double, c_p, i32, c_p]
+    lib.pesto_poses_last_error.restype = ctypes.c_char_p
+    lib.pesto_poses_last_error.argtypes = []
+    lib.pesto_poses_scores.argtypes = [c_p, i64, i64, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_float, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_poses_slide.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p, ctypes.c_float, ctypes.c_float, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_poses_materialize.argtypes = [c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p, i32, c_p]
+    lib.pesto_poses_top.argtypes = [c_p, i64, i64, c_p, c_p, i32, c_p, P(i64), i32, c_p]
     lib.pesto_lddt_last_error.restype = ctypes.c_char_p
     lib.pesto_lddt_last_error.argtypes = []
     lib.pesto_lddt_pairs.argtypes = [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, i32, ctypes.c_float, ctypes.c_double, i64, c_p, c_p, c_p, P(i64), i32, c_p]
@@ -288,17 +296,17 @@ def load():
                         "pesto_hbonds_last_error", "pesto_cluster_last_error", "pesto_peaks_last_error", "pesto_rank_last_error", "pesto_surface_last_error",
                         "pesto_train_last_error", "pesto_dockq_last_error", "pesto_lddt_last_error", "pesto_tmscore_last_error",
                         "pesto_dynamics_last_error", "pesto_align_last_error", "pesto_structalign_last_error", "pesto_chainmap_last_error",
-                        "pesto_qsscore_last_error", "pesto_enm_last_error"):
+                        "pesto_qsscore_last_error", "pesto_enm_last_error", "pesto_poses_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib
 
 
 def check(rc, last_error=None):
-    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are twenty-three channels:
+    """Raises PestoError (code = rc) unless rc == 0. ``last_error``: the function that holds the message. There are twenty-four channels:
     pesto_last_error (the default: the forward pass and everything else of pesto_api) and one per analysis group, pesto_eval_last_error,
     pesto_patches_last_error, pesto_contacts_last_error, pesto_trajectory_last_error, pesto_sasa_last_error, pesto_dssp_last_error, pesto_docking_last_error,
-    pesto_hbonds_last_error, pesto_cluster_last_error, pesto_peaks_last_error, pesto_dockq_last_error, pesto_lddt_last_error, pesto_tmscore_last_error, pesto_align_last_error, pesto_structalign_last_error, pesto_chainmap_last_error, pesto_qsscore_last_error, pesto_dynamics_last_error, pesto_enm_last_error, pesto_rank_last_error, pesto_surface_last_error and pesto_train_last_error."""
+    pesto_hbonds_last_error, pesto_cluster_last_error, pesto_peaks_last_error, pesto_dockq_last_error, pesto_poses_last_error, pesto_lddt_last_error, pesto_tmscore_last_error, pesto_align_last_error, pesto_structalign_last_error, pesto_chainmap_last_error, pesto_qsscore_last_error, pesto_dynamics_last_error, pesto_enm_last_error, pesto_rank_last_error, pesto_surface_last_error and pesto_train_last_error."""
     if rc != 0:
         msg = (last_error or load().pesto_last_error)()
         err = PestoError(f"libpesto_hip error {rc}: {msg.decode() if msg else '?'}")

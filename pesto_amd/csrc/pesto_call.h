@@ -1,5 +1,5 @@
 // pesto_call.h - the host plumbing of one analysis call (pesto_eval / patches / contacts / trajectory / sasa / dssp / rank / surface /
-// docking / dockq / hbonds / lddt / tmscore / align / structalign / cluster / peaks / dynamics / enm .hip, and the message channel of pesto_train.hip): the group's message
+// docking / dockq / poses / hbonds / lddt / tmscore / align / structalign / cluster / peaks / dynamics / enm .hip, and the message channel of pesto_train.hip): the group's message
 // channel, the handle's synchronisation, the offsets check, the launch shape and the call's one stream-ordered allocation with its staged
 // copies, its cleared buffers and the read of the device's verdict.
 //

@@ -1,5 +1,5 @@
 // pesto_cellgrid.h - the float32 uniform cell grid of the project's neighbour searches: the contact searches (interface labels,
-// pesto_eval.hip; dataset contacts, pesto_contacts.hip), lDDT's reference list (pesto_lddt.hip), the elastic network's spring list (pesto_enm.hip) and the k-NN topology (pesto_knn.hip);
+// pesto_eval.hip; dataset contacts, pesto_contacts.hip), lDDT's reference list (pesto_lddt.hip), the elastic network's spring list (pesto_enm.hip), the receptor's grid of the pose scoring (pesto_poses.hip, which walks the rows with a wave) and the k-NN topology (pesto_knn.hip);
 // and torch.norm's distance. The scans: pesto_scan.h.
 //
 // The contact searches replace the reference's dense torch distance matrix per pair of subunits (locate_contacts / extract_all_contacts,

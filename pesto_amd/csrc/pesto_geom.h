@@ -1,5 +1,5 @@
 // pesto_geom.h - the geometry the analysis groups share (pesto_hbonds.hip, pesto_lddt.hip, pesto_cluster.hip, pesto_peaks.hip,
-// pesto_dynamics.hip, and pesto_trajectory.hip, pesto_docking.hip and pesto_dockq.hip through pesto_fit.h): the float32 squared distance
+// pesto_dynamics.hip, pesto_poses.hip, and pesto_trajectory.hip, pesto_docking.hip and pesto_dockq.hip through pesto_fit.h): the float32 squared distance
 // of NumPy and torch, the host's derivation of squared-distance thresholds from it, the workgroup sum in double and the rotation of a
 // Kabsch superposition (kabsch_rotation: the one superposition fit, pesto_fit.h; kabsch_trace: pesto_cluster.hip; jacobi_angle). Also one
 // edge of the model's geometry (r, |r|, the fix-up) for the backward of the geometry pass (pesto_train.hip).

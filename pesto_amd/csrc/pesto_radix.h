@@ -1,4 +1,4 @@
-// pesto_radix.h - the library's one sort, for the ranking columns (pesto_rank.hip) and the dataset contacts (pesto_contacts.hip): a stable
+// pesto_radix.h - the library's one sort, for the ranking columns (pesto_rank.hip), the dataset contacts (pesto_contacts.hip) and the best poses (pesto_poses.hip): a stable
 // LSD radix sort of 64-bit keys on the bits [bit_lo, bit_lo + 8 n_pass). 8-bit digits, per pass a histogram per workgroup tile, one scan
 // of the [digit][tile] counters and a scatter that is stable within the pass (ranks by __ballot per wave, wave offsets through LDS); the
 // keys are double-buffered and a pass whose counters show one occupied bucket moves nothing (the buffers' roles are device state,
