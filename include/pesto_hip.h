@@ -1096,9 +1096,10 @@ enum {
  * chain_score_out float32 [F,Cr] = s(a, mapping[a]) / (finite slots of a), 0 where unmapped; n_mapped_out int32; rotation_out double
  * [F,3,3] and translation_out double [F,3]: x' = x R + t. A frame with an infinite coordinate (on either side) or without a seed: score
  * and transform NaN, chain_score 0, mapping, seed and round -1, n_mapped 0.
- * The scalar arguments are checked on the host; offsets and groups by a kernel before anything dereferences them: a refused call
- * returns PESTO_ERR_INVALID and writes nothing. No atomics on the results: every output is bit-identical from call to call, between
- * host and device pointers and between a frame alone and in a batch. */
+ * The scalar arguments are checked on the host, and so are offsets and groups (device arrays, at most 65 ints each, are copied to the
+ * host on `stream` first), before anything is launched: a refused call returns PESTO_ERR_INVALID, launches nothing and writes nothing.
+ * No atomics on the results: every output is bit-identical from call to call, between host and device pointers and between a frame
+ * alone and in a batch. */
 int pesto_chainmap(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr, int32_t Cm, const int32_t* ref_offsets, const int32_t* ref_group,
                    const int32_t* offsets, const int32_t* group, const float* xyz_ref, const float* xyz, double norm_len, double d0, int32_t n_iter,
                    double scale, float* score_out, int32_t* mapping_out, float* chain_score_out, int32_t* n_mapped_out, int32_t* seed_out,
@@ -1114,8 +1115,8 @@ int pesto_chainmap(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr
  *
  * The layout is that of the chain mapping group (one point per residue, customarily CB, CA for glycine; all chains of a group share the
  * slots of the group; a residue a chain lacks is NaN), with its limits PESTO_CHAINMAP_MAX_*; the four int32 layout arrays live where ptr_kind
- * says, like the coordinates, as the chain mapping group takes them (device arrays, at most 65 ints each, are copied to the host on
- * `stream` first: the job lists are made there and the layout is checked there). Definition, in double from the float32 inputs:
+ * says, like the coordinates, and are checked as the chain mapping group checks them, by the same code and before anything is launched
+ * (device arrays are copied to the host on `stream` first; the job lists are made there too). Definition, in double from the float32 inputs:
  *     w(d) = 1 for d <= 5, exp(-2 ((d - 5) / 4.28)^2) for 5 < d < 12, 0 for d >= 12 (angstroms after scale)
  *     a mapping m[a] = the model chain under reference chain a or -1, one to one, within groups; interface (a, a'), a < a', is mapped if
  *     both are; a slot pair (r, s) of it is common if y[a,r], y[a',s], x[b,r], x[b',s] are finite (b = m[a], b' = m[a']);

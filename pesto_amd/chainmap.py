@@ -15,8 +15,8 @@ on both sides, share one residue index space: they have the same length L_g and 
 residue a chain lacks has NaN coordinates. A group may occur on one side only: its chains stay unmapped. One point per residue,
 normally CA. scale multiplies distances (the default 10 turns nanometres into angstroms). The lead argument xyz decides where a call
 runs (_lib.Side): NumPy in, NumPy out; ROCm tensors in, ROCm tensors out on torch's current stream. There is no CPU or PyTorch fallback.
-Arguments are checked on the host before any launch (ValueError); offsets and groups are checked again by a kernel whose verdict is
-read before anything is written.
+Arguments are checked on the host before any launch (ValueError); the library checks offsets and groups again, on the host as well (it
+brings device arrays over first), and launches nothing when it refuses them.
 
 Definition. Everything is in double from the float32 inputs.
     L_norm        the reference's residues with finite coordinates, over all chains; norm_len= overrides it
@@ -72,6 +72,14 @@ def seed_pair(seed, n_model_chains):
     return divmod(int(seed), int(n_model_chains))
 
 
+def _offsets(offsets, N, name):
+    """offsets as int64 [C + 1], C >= 1: from 0 to N (None: wherever they end) in ascending order"""
+    o = np.asarray(_lib.host(offsets)).reshape(-1).astype(np.int64)
+    if o.size < 2 or o[0] != 0 or (N is not None and o[-1] != N) or np.any(np.diff(o) <= 0):
+        raise ValueError(f"{name}offsets must start at 0{'' if N is None else f', end at {N}'} and ascend")
+    return o
+
+
 def _chains(offsets, group, N, name):
     """(offsets int32 [C + 1], group int64 [C]) of one side, checked"""
     o = np.asarray(_lib.host(offsets)).reshape(-1)
@@ -81,9 +89,7 @@ def _chains(offsets, group, N, name):
     C = g.size
     if not 1 <= C <= MAX_CHAINS or o.size != C + 1:
         raise ValueError(f"{name}group names 1 to {MAX_CHAINS} chains and {name}offsets has one entry more, got {C} and {o.size}")
-    o = o.astype(np.int64)
-    if o[0] != 0 or o[-1] != N or np.any(np.diff(o) <= 0):
-        raise ValueError(f"{name}offsets must start at 0, end at {N} and ascend")
+    o = _offsets(o, N, name)
     L = np.diff(o)
     if L.min() < 3 or L.max() > MAX_LENGTH:
         raise ValueError(f"{name}offsets: every chain has 3 to {MAX_LENGTH} slots, got {int(L.min())} to {int(L.max())}")
@@ -101,10 +107,17 @@ def _positive(value, name, default):
     return v
 
 
-def chain_map(xyz_ref, ref_offsets, ref_group, xyz, offsets, group, *, norm_len=None, d0=None, n_iter=5, scale=10.0, model=None):
-    """ChainMap(score float32 [F], mapping int32 [F, Cr], chain_score float32 [F, Cr], n_mapped int32 [F], seed int32 [F], round int32 [F],
-    rotation float64 [F, 3, 3], translation float64 [F, 3]) of the F models xyz against the reference: see the module's definition."""
-    from .tmscore import default_d0
+def _numeric(a):
+    """the module whose functions take a: torch for a tensor, NumPy for an array"""
+    if _lib.is_torch(a):
+        import torch
+        return torch
+    return np
+
+
+def _oligomer(xyz_ref, ref_offsets, ref_group, xyz, offsets, group):
+    """The input every oligomer entry point takes (chain_map, qsscore.qs_score, qsscore.qs_map), checked: (y [1, Nr, 3], x [F, Nm, 3],
+    F, Nr, Nm, ro, rg, mo, mg) with int32 offsets and the int32 group ids numbered densely over both sides."""
     y = _frames(xyz_ref, "xyz_ref")
     if int(y.shape[0]) != 1:
         raise ValueError(f"xyz_ref must be the one reference, [Nr, 3] or [1, Nr, 3], got {int(y.shape[0])} frames")
@@ -121,16 +134,20 @@ def chain_map(xyz_ref, ref_offsets, ref_group, xyz, offsets, group, *, norm_len=
     for g, L in zip(np.concatenate([rg, mg]), np.concatenate([np.diff(ro), np.diff(mo)])):
         if length.setdefault(int(g), int(L)) != int(L):
             raise ValueError(f"all chains of a group share its slots: a chain of {int(L)} slots in a group of {length[int(g)]}")
+    if bool(_numeric(y).isinf(y).any()):
+        raise ValueError("xyz_ref: a coordinate of the reference is infinite (a missing residue is NaN)")
+    return y, x, F, Nr, Nm, ro, rg, mo, mg
+
+
+def chain_map(xyz_ref, ref_offsets, ref_group, xyz, offsets, group, *, norm_len=None, d0=None, n_iter=5, scale=10.0, model=None):
+    """ChainMap(score float32 [F], mapping int32 [F, Cr], chain_score float32 [F, Cr], n_mapped int32 [F], seed int32 [F], round int32 [F],
+    rotation float64 [F, 3, 3], translation float64 [F, 3]) of the F models xyz against the reference: see the module's definition."""
+    from .tmscore import default_d0
+    y, x, F, Nr, Nm, ro, rg, mo, mg = _oligomer(xyz_ref, ref_offsets, ref_group, xyz, offsets, group)
     if isinstance(n_iter, bool) or n_iter != int(n_iter) or not 1 <= n_iter <= MAX_ITER:
         raise ValueError(f"1 <= n_iter <= {MAX_ITER} (an integer) expected, got {n_iter!r}")
     sc = _positive(scale, "scale", 10.0)
-    if _lib.is_torch(y):
-        import torch
-        infinite, n_finite = bool(torch.isinf(y).any()), int(torch.isfinite(y[0]).all(1).sum())
-    else:
-        infinite, n_finite = bool(np.isinf(y).any()), int(np.isfinite(y[0]).all(1).sum())
-    if infinite:
-        raise ValueError("xyz_ref: a coordinate of the reference is infinite (a missing residue is NaN)")
+    n_finite = int(_numeric(y).isfinite(y[0]).all(1).sum())
     if norm_len is None and n_finite < 1:
         raise ValueError("xyz_ref: the reference has no residue with finite coordinates")
     ln = _positive(norm_len, "norm_len", n_finite)
@@ -157,13 +174,10 @@ def apply_mapping(xyz, offsets, mapping, ref_offsets):
     mapped model chain must have its reference chain's length (ValueError)."""
     x = _frames(xyz, "xyz")
     F, Nm = int(x.shape[0]), int(x.shape[1])
-    mo = np.asarray(_lib.host(offsets)).reshape(-1).astype(np.int64)
-    ro = np.asarray(_lib.host(ref_offsets)).reshape(-1).astype(np.int64)
+    mo, ro = _offsets(offsets, Nm, ""), _offsets(ref_offsets, None, "ref_")
     m = np.asarray(_lib.host(mapping)).astype(np.int64)
     m = m[None] if m.ndim == 1 else m
     Cr, Cm = ro.size - 1, mo.size - 1
-    if Cr < 1 or Cm < 1 or ro[0] != 0 or mo[0] != 0 or mo[-1] != Nm or np.any(np.diff(ro) <= 0) or np.any(np.diff(mo) <= 0):
-        raise ValueError("offsets must start at 0, ascend and end at the number of the model's residues; ref_offsets likewise from 0")
     if m.ndim != 2 or m.shape[1] != Cr or m.shape[0] not in (1, F) or m.min() < -1 or m.max() >= Cm:
         raise ValueError(f"mapping must be [{Cr}] or [{F}, {Cr}] with model chains in [-1, {Cm}), got {list(m.shape)}")
     Lr, Lm = np.diff(ro), np.diff(mo)

@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["pesto_schema.cpp", "pesto_kernels.hip", "pesto_knn.hip", "pesto_node.hip", "pesto_edge.hip", "pesto_eval.hip", "pesto_patches.hip", "pesto_contacts.hip", "pesto_trajectory.hip", "pesto_docking.hip", "pesto_dockq.hip", "pesto_poses.hip", "pesto_lddt.hip", "pesto_tmscore.hip", "pesto_align.hip", "pesto_structalign.hip", "pesto_chainmap.hip", "pesto_qsscore.hip", "pesto_dynamics.hip", "pesto_enm.hip", "pesto_hbonds.hip", "pesto_cluster.hip", "pesto_peaks.hip", "pesto_rank.hip", "pesto_surface.hip", "pesto_sasa.hip", "pesto_dssp.hip", "pesto_train.hip", "pesto_api.hip"]
-HEADERS = ["pesto_schema.h", "pesto_kernels.h", "pesto_mfma_common.h", "pesto_fin_rendezvous.inc", "pesto_edge_node_waves.inc", "pesto_call.h", "pesto_scan.h", "pesto_radix.h", "pesto_cellgrid.h", "pesto_geom.h", "pesto_fit.h", "pesto_alignwave.h", "pesto_tmsearch.h", "pesto_mma64.h", "pesto_ritz.h", os.path.join("..", "..", "include", "pesto_hip.h")]
+HEADERS = ["pesto_schema.h", "pesto_kernels.h", "pesto_mfma_common.h", "pesto_fin_rendezvous.inc", "pesto_edge_node_waves.inc", "pesto_call.h", "pesto_oligomer.h", "pesto_scan.h", "pesto_radix.h", "pesto_cellgrid.h", "pesto_geom.h", "pesto_fit.h", "pesto_alignwave.h", "pesto_tmsearch.h", "pesto_mma64.h", "pesto_ritz.h", os.path.join("..", "..", "include", "pesto_hip.h")]
 OUT = os.path.join(HERE, "libpesto_hip.so")
 # host-only structure I/O library (include/pesto_io.h): plain C++, no HIP runtime, safe in forked data-loader workers
 IO_SOURCE = "pesto_io.cpp"

@@ -1,7 +1,8 @@
 // pesto_call.h - the host plumbing of one analysis call (pesto_eval / patches / contacts / trajectory / sasa / dssp / rank / surface /
 // docking / dockq / poses / hbonds / lddt / tmscore / align / structalign / cluster / peaks / dynamics / enm .hip, and the message channel of pesto_train.hip): the group's message
 // channel, the handle's synchronisation, the offsets check, the launch shape and the call's one stream-ordered allocation with its staged
-// copies, its cleared buffers and the read of the device's verdict.
+// copies, its cleared buffers and the read of the device's verdict. (pesto_chainmap.hip and pesto_qsscore.hip come here through
+// pesto_oligomer.h, which adds the layout of an oligomer and its check.)
 //
 // The protocol of one call: declare the buffers (a cleared one with its fill byte) -> upload() -> launch -> verdict(), where the host
 // needs the device's verdict before it goes on (to size a list: list_tail of pesto_scan.h; to refuse before anything is written;

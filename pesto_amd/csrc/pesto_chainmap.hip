@@ -1,7 +1,8 @@
 // pesto_chainmap.hip - the chain mapping of oligomers: which model chain lies on which reference chain, for every frame of a run or every
 // decoy of a set in one call, so that lDDT, DockQ and the TM-score of a complex see the copies of an entity in the reference's order.
 //
-// The C entry point (include/pesto_hip.h) lives here too, on the call plumbing of pesto_call.h, with a message channel of its own.
+// The C entry point (include/pesto_hip.h) lives here too, on the call plumbing of pesto_call.h, with a message channel of its own; the
+// sizes, the layout (checked on the host before anything is launched) and the frames' scan for infinities are pesto_oligomer.h's.
 //
 // The mapping is a maximum over superpositions, found by a search like the TM-score's (pesto_tmscore.hip): from every seed, a chain pair of
 // one entity, the model is fitted onto the reference, every chain pair of every entity is scored under that fit, the copies are assigned
@@ -14,8 +15,8 @@
 #include <climits>
 #include <cmath>
 
-#include "pesto_call.h"
 #include "pesto_fit.h"
+#include "pesto_oligomer.h"
 
 namespace pesto {
 
@@ -37,52 +38,11 @@ struct CmBest {
     int seed, round, n_mapped, pad;
 };
 
-__device__ __forceinline__ bool finite3(const float* p) {
-    return fabsf(p[0]) <= 3.402823466e38f && fabsf(p[1]) <= 3.402823466e38f && fabsf(p[2]) <= 3.402823466e38f;
-}
-
-// ------------------------------------------------------------------------------------------------ the layout check
-// One thread reads the four small arrays: offsets from 0 to N in ascending order (bit 0), group ids in [0, MAX_GROUPS) (bit 1), chains of
-// 3 to MAX_LENGTH slots and of one length within a group, on both sides (bit 2), at most MAX_GROUP chains of a group on a side (bit 3).
-// Every other kernel returns at once when a bit is set, so nothing dereferences a layout that was refused.
-__global__ __launch_bounds__(64) void k_cm_check(int Cr, int Cm, int Nr, int Nm, const int* __restrict__ ro, const int* __restrict__ rg,
-                                                 const int* __restrict__ mo, const int* __restrict__ mg, int* __restrict__ err) {
-    if (threadIdx.x != 0) return;
-    int e = 0;
-    for (int side = 0; side < 2; ++side) {
-        const int* off = side ? mo : ro;
-        const int* grp = side ? mg : rg;
-        const int C = side ? Cm : Cr, N = side ? Nm : Nr;
-        if (off[0] != 0 || off[C] != N) e |= 1;
-        for (int c = 0; c < C; ++c) {
-            const long long len = (long long)off[c + 1] - off[c];
-            if (len <= 0) e |= 1;
-            else if (len < 3 || len > PESTO_CHAINMAP_MAX_LENGTH) e |= 4;
-            if (grp[c] < 0 || grp[c] >= PESTO_CHAINMAP_MAX_GROUPS) e |= 2;
-        }
-    }
-    if (!e)
-        for (int side = 0; side < 2; ++side) {
-            const int* off = side ? mo : ro;
-            const int* grp = side ? mg : rg;
-            const int C = side ? Cm : Cr;
-            for (int c = 0; c < C; ++c) {
-                const int len = off[c + 1] - off[c];
-                int n = 0;
-                for (int k = 0; k < C; ++k) n += grp[k] == grp[c];
-                if (n > MAX_G) e |= 8;
-                for (int k = 0; k < Cr; ++k)
-                    if (rg[k] == grp[c] && ro[k + 1] - ro[k] != len) e |= 4;
-            }
-        }
-    if (e) *err = e;
-}
-
+// ------------------------------------------------------------------------------------------------ the reference
 // cnt[a] = the slots of reference chain a with finite coordinates: the divisor of chain_score; -1 if the chain has an infinite
-// coordinate. One wave per chain.
-__global__ __launch_bounds__(64) void k_cm_ref_counts(const int* __restrict__ ro, const float* __restrict__ ref, const int* __restrict__ err,
-                                                      int* __restrict__ cnt) {
-    if (*err) return;
+// coordinate, which also raises ref_bad for k_oligomer_frames (an integer OR: the same whatever the order). One wave per chain.
+__global__ __launch_bounds__(64) void k_cm_ref_counts(const int* __restrict__ ro, const float* __restrict__ ref, int* __restrict__ cnt,
+                                                      int* __restrict__ ref_bad) {
     const int a = blockIdx.x, r0 = ro[a], L = ro[a + 1] - r0;
     int n = 0, inf = 0;
     for (int k = threadIdx.x; k < L; k += 64) {
@@ -92,19 +52,10 @@ __global__ __launch_bounds__(64) void k_cm_ref_counts(const int* __restrict__ ro
     }
     n = wave_sum(n);
     inf = wave_sum(inf);
-    if (threadIdx.x == 0) cnt[a] = inf ? -1 : n;
-}
-
-// bad[f] = frame f, or the reference, has an infinite coordinate: scanned once per frame, read by every share of the frame
-__global__ __launch_bounds__(NT) void k_cm_frames(int Cr, int Nm, const float* __restrict__ xyz, const int* __restrict__ ref_cnt,
-                                                  const int* __restrict__ err, int* __restrict__ bad_out) {
-    if (*err) return;
-    const float* X = xyz + (size_t)blockIdx.x * Nm * 3;
-    int bad = 0;
-    for (size_t k = threadIdx.x; k < (size_t)Nm * 3; k += NT) bad |= fabsf(X[k]) == INFINITY;
-    for (int c = threadIdx.x; c < Cr; c += NT) bad |= ref_cnt[c] < 0;
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0) bad_out[blockIdx.x] = bad ? 1 : 0;
+    if (threadIdx.x == 0) {
+        cnt[a] = inf ? -1 : n;
+        if (inf) atomicOr(ref_bad, 1);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the search
@@ -113,20 +64,19 @@ __global__ __launch_bounds__(NT) void k_cm_frames(int Cr, int Nm, const float* _
 __global__ __launch_bounds__(NT) void k_cm_search(int shares, int Cr, int Cm, int Nr, int Nm, int n_iter, double d0, double scale, int cap,
                                                   const int* __restrict__ ro_g, const int* __restrict__ rg_g, const int* __restrict__ mo_g,
                                                   const int* __restrict__ mg_g, const float* __restrict__ ref, const float* __restrict__ xyz,
-                                                  const int* __restrict__ err, const int* __restrict__ frame_bad, int* lists, CmBest* __restrict__ out) {
+                                                  const int* __restrict__ frame_bad, int* lists, CmBest* __restrict__ out) {
     __shared__ double s_f[1 << MAX_G];          // the assignment's table: the best sum of the first popcount(mask) rows placed on mask
     __shared__ double s_S[MAX_G * MAX_G];       // the pair sums of one group, [reference chain][model chain]
     __shared__ double s_red[NW], s_R[9], s_cs[MAX_C], s_rv[NW], s_total;
     __shared__ int s_ro[MAX_C + 1], s_mo[MAX_C + 1], s_rg[MAX_C], s_mg[MAX_C], s_map[MAX_C], s_prev[MAX_C], s_fit[MAX_C];
     __shared__ int s_ra[MAX_G], s_mb[MAX_G], s_nr, s_nm, s_wcnt[NW], s_rm[NW], s_flag, s_gmax;
     __shared__ CmBest s_best;
-    if (*err) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned fl = blockIdx.x / (unsigned)shares, sh = blockIdx.x % (unsigned)shares;
     const float* X = xyz + (size_t)fl * Nm * 3;
     int* lr = lists + (size_t)blockIdx.x * 2 * cap;
     int* lm = lr + cap;
-    if (frame_bad[fl]) {                        // (k_cm_frames: the same verdict for every share of the frame)
+    if (frame_bad[fl]) {                        // (k_oligomer_frames: the same verdict for every share of the frame)
         if (tid == 0) out[blockIdx.x].seed = SEED_BAD;
         return;
     }
@@ -319,10 +269,9 @@ __global__ __launch_bounds__(NT) void k_cm_search(int shares, int Cr, int Cm, in
 // One wave per frame: the maximum total over the frame's shares (ties: the lowest seed), the quotients, rounded once. A frame with an
 // infinite coordinate or without a seed: NaN score and fit, mapping, seed and round -1.
 __global__ __launch_bounds__(64) void k_cm_final(int shares, int Cr, double lnorm, const CmBest* __restrict__ parts, const int* __restrict__ ref_cnt,
-                                                 const int* __restrict__ err, float* __restrict__ score_out, int* __restrict__ map_out,
-                                                 float* __restrict__ cs_out, int* __restrict__ nmap_out, int* __restrict__ seed_out,
-                                                 int* __restrict__ round_out, double* __restrict__ rot_out, double* __restrict__ tr_out) {
-    if (*err) return;
+                                                 float* __restrict__ score_out, int* __restrict__ map_out, float* __restrict__ cs_out,
+                                                 int* __restrict__ nmap_out, int* __restrict__ seed_out, int* __restrict__ round_out,
+                                                 double* __restrict__ rot_out, double* __restrict__ tr_out) {
     const size_t u = blockIdx.x;
     const CmBest* P = parts + u * (size_t)shares;
     const int lane = threadIdx.x;
@@ -369,13 +318,13 @@ int pesto_chainmap(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr
     if (!ref_offsets || !ref_group || !offsets || !group || !xyz_ref || !xyz || !score_out || !mapping_out || !chain_score_out || !n_mapped_out ||
         !seed_out || !round_out || !rotation_out || !translation_out)
         return fail(PESTO_ERR_INVALID, "bad arguments");
-    if (F < 1 || F > PESTO_CHAINMAP_MAX_FRAMES || Nr < 3 || Nr > 0x3fffffff || Nm < 3 || Nm > 0x3fffffff)
-        return fail(PESTO_ERR_INVALID, "1 to 2^23 frames and 3 <= Nr, Nm < 2^30 residues");
-    if (Cr < 1 || Cr > MAX_C || Cm < 1 || Cm > MAX_C) return fail(PESTO_ERR_INVALID, "1 to %d chains on each side", MAX_C);
+    if (int rc = check_oligomer_sizes(F, Nr, Nm, Cr, Cm, scale)) return rc;
     if (n_iter < 1 || n_iter > PESTO_CHAINMAP_MAX_ITER) return fail(PESTO_ERR_INVALID, "1 <= n_iter <= %d", PESTO_CHAINMAP_MAX_ITER);
-    if (!(std::isfinite(scale) && scale > 0.0)) return fail(PESTO_ERR_INVALID, "scale must be positive and finite");
     if (!(std::isfinite(norm_len) && norm_len > 0.0) || !(std::isfinite(d0) && d0 > 0.0)) return fail(PESTO_ERR_INVALID, "norm_len and d0 must be positive and finite");
     if (int rc = begin(m, ptr_kind)) return rc;
+    // the layout is checked on the host before anything is declared or launched: a refused call writes nothing
+    OligomerLayout lay;
+    if (int rc = fetch_layout("chainmap", Nr, Nm, Cr, Cm, ref_offsets, ref_group, offsets, group, ptr_kind, stream, lay)) return rc;
     const int64_t cap = std::min(Nr, Nm);
     // the shares of a frame and the frames of one launch: their gathered slot lists (8 cap bytes a workgroup) fit the workspace
     const int shares = (int)std::min<int64_t>(std::min<int64_t>((int64_t)Cr * Cm, std::max<int64_t>(1, (TARGET_GROUPS + F - 1) / F)),
@@ -389,34 +338,25 @@ int pesto_chainmap(pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, int32_t Cr
               iNm = bf.output(n_mapped_out, (size_t)F * 4), iSd = bf.output(seed_out, (size_t)F * 4), iRd = bf.output(round_out, (size_t)F * 4),
               iRot = bf.output(rotation_out, (size_t)F * 72), iTr = bf.output(translation_out, (size_t)F * 24);
     const int iP = bf.scratch((size_t)chunk * shares * sizeof(CmBest)), iL = bf.scratch((size_t)chunk * shares * cap * 8), iCn = bf.scratch(MAX_C * 4, 0), iBad = bf.scratch((size_t)chunk * 4),
-              iSt = bf.scratch(sizeof(int), 0);
-    int herr = 0;
-    int rc = bf.upload();
+              iRb = bf.scratch(sizeof(int), 0);
+    const int rc = bf.upload();
     if (rc == 0) {
         const int* ro = bf.ptr<const int>(iRo);
         const int* rg = bf.ptr<const int>(iRg);
         const int* mo = bf.ptr<const int>(iMo);
         const int* mg = bf.ptr<const int>(iMg);
-        const int* st = bf.ptr<const int>(iSt);
-        hipLaunchKernelGGL(k_cm_check, dim3(1), dim3(64), 0, bf.stm, (int)Cr, (int)Cm, (int)Nr, (int)Nm, ro, rg, mo, mg, bf.ptr<int>(iSt));
-        hipLaunchKernelGGL(k_cm_ref_counts, dim3((unsigned)Cr), dim3(64), 0, bf.stm, ro, bf.ptr<const float>(iY), st, bf.ptr<int>(iCn));
+        hipLaunchKernelGGL(k_cm_ref_counts, dim3((unsigned)Cr), dim3(64), 0, bf.stm, ro, bf.ptr<const float>(iY), bf.ptr<int>(iCn), bf.ptr<int>(iRb));
         for (int64_t f0 = 0; f0 < F; f0 += chunk) {
             const int64_t nf = std::min(chunk, F - f0);
-            hipLaunchKernelGGL(k_cm_frames, dim3((unsigned)nf), dim3(NT), 0, bf.stm, (int)Cr, (int)Nm, bf.ptr<const float>(iX) + (size_t)f0 * Nm * 3,
-                               bf.ptr<const int>(iCn), st, bf.ptr<int>(iBad));
+            hipLaunchKernelGGL(k_oligomer_frames, dim3((unsigned)nf), dim3(OLIGOMER_NT), 0, bf.stm, (int)Nm, bf.ptr<const float>(iX) + (size_t)f0 * Nm * 3,
+                               bf.ptr<const int>(iRb), bf.ptr<int>(iBad));
             hipLaunchKernelGGL(k_cm_search, dim3((unsigned)(nf * shares)), dim3(NT), 0, bf.stm, shares, (int)Cr, (int)Cm, (int)Nr, (int)Nm, (int)n_iter, d0, scale,
-                               (int)cap, ro, rg, mo, mg, bf.ptr<const float>(iY), bf.ptr<const float>(iX) + (size_t)f0 * Nm * 3, st, bf.ptr<const int>(iBad), bf.ptr<int>(iL),
+                               (int)cap, ro, rg, mo, mg, bf.ptr<const float>(iY), bf.ptr<const float>(iX) + (size_t)f0 * Nm * 3, bf.ptr<const int>(iBad), bf.ptr<int>(iL),
                                bf.ptr<CmBest>(iP));
-            hipLaunchKernelGGL(k_cm_final, dim3((unsigned)nf), dim3(64), 0, bf.stm, shares, (int)Cr, norm_len, bf.ptr<const CmBest>(iP), bf.ptr<const int>(iCn), st,
+            hipLaunchKernelGGL(k_cm_final, dim3((unsigned)nf), dim3(64), 0, bf.stm, shares, (int)Cr, norm_len, bf.ptr<const CmBest>(iP), bf.ptr<const int>(iCn),
                                bf.ptr<float>(iSc) + f0, bf.ptr<int>(iMp) + f0 * Cr, bf.ptr<float>(iCs) + f0 * Cr, bf.ptr<int>(iNm) + f0, bf.ptr<int>(iSd) + f0,
                                bf.ptr<int>(iRd) + f0, bf.ptr<double>(iRot) + f0 * 9, bf.ptr<double>(iTr) + f0 * 3);
         }
     }
-    // a refused call writes nothing: the check's verdict is read before any output is copied back
-    if (rc == 0) rc = bf.verdict(iSt, &herr, sizeof herr, "chainmap");
-    if (rc == 0 && (herr & 1)) rc = fail(PESTO_ERR_INVALID, "chainmap: offsets must start at 0, end at the number of residues and ascend");
-    else if (rc == 0 && (herr & 2)) rc = fail(PESTO_ERR_INVALID, "chainmap: group ids must lie in [0, %d)", PESTO_CHAINMAP_MAX_GROUPS);
-    else if (rc == 0 && (herr & 4)) rc = fail(PESTO_ERR_INVALID, "chainmap: a chain must have 3 to %d slots, as many as every chain of its group", PESTO_CHAINMAP_MAX_LENGTH);
-    else if (rc == 0 && (herr & 8)) rc = fail(PESTO_ERR_INVALID, "chainmap: at most %d chains of a group on a side", PESTO_CHAINMAP_MAX_GROUP);
     return bf.finish(rc, "chainmap");
 }

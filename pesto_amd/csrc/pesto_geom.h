@@ -23,6 +23,11 @@ __device__ __forceinline__ float dist2(float ax, float ay, float az, float bx, f
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
+// the point p[0 .. 2] has three finite coordinates (neither NaN nor infinite)
+__device__ __forceinline__ bool finite3(const float* p) {
+    return fabsf(p[0]) <= 3.402823466e38f && fabsf(p[1]) <= 3.402823466e38f && fabsf(p[2]) <= 3.402823466e38f;
+}
+
 
 // One edge of the model's geometry (src/model_operations.py:8-14) in the float32 operations of the forward's geometry pass (k_unpack1 /
 // k_unpack2, pesto_kernels.hip, whose text is pinned by the committed profile's source stamp): the same expressions with the same

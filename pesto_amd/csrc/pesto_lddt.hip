@@ -86,16 +86,12 @@ struct MetaPayload {
 // and sits on the first finite atom of its structure (the origin for a structure without one): such an atom has no pairs by the
 // definition, and the grid's bounding box (grid_build's set-up) then only ever sees finite coordinates and is no larger than the finite atoms'
 // own. k_lddt_anchor, one workgroup per structure: anchor[s] = the first atom with three finite coordinates, or -1.
-__device__ __forceinline__ bool finite3(const float* __restrict__ Y, int i) {
-    return isfinite(Y[3 * (size_t)i]) && isfinite(Y[3 * (size_t)i + 1]) && isfinite(Y[3 * (size_t)i + 2]);
-}
-
 __global__ __launch_bounds__(NT) void k_lddt_anchor(const int* __restrict__ offsets, const float* __restrict__ Y, int* __restrict__ anchor) {
     __shared__ int first[NT];
     const int s0 = offsets[blockIdx.x], s1 = offsets[blockIdx.x + 1];
     int mine = 0x7fffffff;
     for (int i = s0 + threadIdx.x; i < s1 && mine == 0x7fffffff; i += NT)
-        if (finite3(Y, i)) mine = i;
+        if (finite3(Y + 3 * (size_t)i)) mine = i;
     first[threadIdx.x] = mine;
     __syncthreads();
     for (int o = NT / 2; o > 0; o >>= 1) {
@@ -113,7 +109,7 @@ __global__ __launch_bounds__(NT) void k_lddt_clean(int N, int n_struct, const in
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= N) return;
     if (res[i] < 0) atomicOr(&st->err, ERR_RES);
-    const bool finite = finite3(Y, i);
+    const bool finite = finite3(Y + 3 * (size_t)i);
     const int a = finite ? i : anchor[struct_of(i, n_struct, offsets)];
 #pragma unroll
     for (int c = 0; c < 3; ++c) Yc[3 * (size_t)i + c] = a < 0 ? 0.f : Y[3 * (size_t)a + c];

@@ -50,9 +50,6 @@ __device__ __forceinline__ float place(const float* row, float t, float x0, floa
 }
 
 __device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }
-__device__ __forceinline__ bool finite3(const float* __restrict__ X, int i) {
-    return finite32(X[3 * (size_t)i]) && finite32(X[3 * (size_t)i + 1]) && finite32(X[3 * (size_t)i + 2]);
-}
 
 // sum of v over the workgroup, the same value in every thread (block_sum's integer sibling). ired: NW ints; two barriers
 __device__ __forceinline__ int block_count(int v, int* ired) {
@@ -84,7 +81,7 @@ __global__ __launch_bounds__(NT) void k_poses_check(long long F, int N_R, int N_
     __shared__ double red[NW];
     const long long k = (long long)blockIdx.x * NT + threadIdx.x;
     int bad = 0;
-    if (grid_R && k < N_R && finite3(grid_R, (int)k)) atomicMin(anchor, (unsigned)k);
+    if (grid_R && k < N_R && finite3(grid_R + 3 * (size_t)k)) atomicMin(anchor, (unsigned)k);
     if (res_R && k < N_R && (unsigned)res_R[k] >= (unsigned)R_R) bad |= 1;
     if (perm_L && k < N_L && (unsigned)perm_L[k] >= (unsigned)N_L) bad |= 1;
     if (off_L && k < R_L) {
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(NT) void k_poses_check(long long F, int N_R, int N_
 __global__ __launch_bounds__(NT) void k_poses_clean(int N_R, const float* __restrict__ X, const unsigned* __restrict__ anchor, float* __restrict__ Xc) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= N_R) return;
-    const unsigned a = finite3(X, i) ? (unsigned)i : *anchor;
+    const unsigned a = finite3(X + 3 * (size_t)i) ? (unsigned)i : *anchor;
 #pragma unroll
     for (int c = 0; c < 3; ++c) Xc[3 * (size_t)i + c] = a == 0xffffffffu ? 0.f : X[3 * (size_t)a + c];
 }
@@ -138,7 +135,7 @@ struct ResiduePayload {
     float4* sorted;
     __device__ void operator()(int pos, int i) const {
         out[pos] = res[i];
-        if (!finite3(X, i)) sorted[pos] = make_float4(NAN, NAN, NAN, __int_as_float(i));
+        if (!finite3(X + 3 * (size_t)i)) sorted[pos] = make_float4(NAN, NAN, NAN, __int_as_float(i));
     }
 };
 

@@ -1,7 +1,8 @@
 // pesto_qsscore.hip - the QS-score of assemblies (Bertoni et al. 2017) with the interface contact score ICS, for a given chain mapping or
 // for the mapping that maximises it, for every frame of a run or every decoy of a set in one call.
 //
-// The C entry points (include/pesto_hip.h) live here too, on the call plumbing of pesto_call.h, with a message channel of their own.
+// The C entry points (include/pesto_hip.h) live here too, on the call plumbing of pesto_call.h, with a message channel of their own; the
+// sizes, the layout and its check on the host and the frames' scan for infinities are pesto_oligomer.h's, shared with pesto_chainmap.hip.
 //
 // Everything rests on a per-frame table of chain-pair terms: entry ((a, a'), (b, b')) holds the five weighted sums and the shared
 // contact count of reference interface (a, a') under the model chain pair (b, b'). pesto_qsscore fills the Cr (Cr - 1) / 2 entries of
@@ -16,8 +17,8 @@
 #include <climits>
 #include <cmath>
 
-#include "pesto_call.h"
 #include "pesto_fit.h"
+#include "pesto_oligomer.h"
 
 namespace pesto {
 
@@ -83,8 +84,9 @@ __global__ __launch_bounds__(NT) void k_qs_ref(int Nr, const float* __restrict__
     if (bad) atomicOr(ref_bad, 1);
 }
 
-// Every row of the mapping: model chains in [-1, Cm), each at most once (bit 0), of the reference chain's group (bit 1). Every other
-// kernel returns at once when a bit is set, so nothing dereferences a mapping that was refused and nothing is written.
+// Every row of the mapping: model chains in [-1, Cm), each at most once (bit 0), of the reference chain's group (bit 1). Every kernel
+// but the two scans for infinities returns at once when a bit is set, so nothing dereferences a mapping that was refused and no result
+// is written.
 __global__ __launch_bounds__(NT) void k_qs_mapcheck(long long rows, int Cr, int Cm, const int* __restrict__ rg, const int* __restrict__ mg,
                                                     const int* __restrict__ mapping, int* __restrict__ err) {
     const long long row = (long long)blockIdx.x * NT + threadIdx.x;
@@ -102,17 +104,6 @@ __global__ __launch_bounds__(NT) void k_qs_mapcheck(long long rows, int Cr, int 
         }
     }
     if (e) atomicOr(err, e);
-}
-
-// bad[f] = frame f, or the reference, has an infinite coordinate
-__global__ __launch_bounds__(NT) void k_qs_frames(int Nm, const float* __restrict__ xyz, const int* __restrict__ ref_bad, const int* __restrict__ err,
-                                                  int* __restrict__ bad_out) {
-    if (*err) return;
-    const float* X = xyz + (size_t)blockIdx.x * Nm * 3;
-    int bad = *ref_bad;
-    for (size_t k = threadIdx.x; k < (size_t)Nm * 3; k += NT) bad |= fabsf(X[k]) == INFINITY;
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0) bad_out[blockIdx.x] = bad ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------ the table (the hot path)
@@ -443,41 +434,10 @@ __global__ __launch_bounds__(64) void k_qs_pick(int n_blocks, int Cr, QsGroups g
 }
 
 // ------------------------------------------------------------------------------------------------ the host side
-// the layout of both sides, checked on the host (qs_run brings device arrays over first), and what the launches need of it
-struct Layout {
-    std::vector<int> ia, iap;           // the reference's chain pairs a < a' in ascending order: the interfaces
-    std::vector<int> ma, map;           // the model's chain pairs
-    int nrb = 1;                        // slot blocks of the longest chain
-};
-
-int check_layout(const char* who, int64_t Nr, int64_t Nm, int Cr, int Cm, const int32_t* ro, const int32_t* rg, const int32_t* mo, const int32_t* mg, Layout& lay) {
-    int len[PESTO_CHAINMAP_MAX_GROUPS], longest = 0;
-    for (int& v : len) v = 0;
-    for (int side = 0; side < 2; ++side) {
-        const int32_t* off = side ? mo : ro;
-        const int32_t* grp = side ? mg : rg;
-        const int C = side ? Cm : Cr;
-        const int64_t N = side ? Nm : Nr;
-        if (off[0] != 0 || off[C] != N || first_unordered(off, C) >= 0)
-            return fail(PESTO_ERR_INVALID, "%s: offsets must start at 0, end at the number of residues and ascend", who);
-        int count[PESTO_CHAINMAP_MAX_GROUPS];
-        for (int& v : count) v = 0;
-        for (int c = 0; c < C; ++c) {
-            if (grp[c] < 0 || grp[c] >= PESTO_CHAINMAP_MAX_GROUPS) return fail(PESTO_ERR_INVALID, "%s: group ids must lie in [0, %d)", who, PESTO_CHAINMAP_MAX_GROUPS);
-            const int L = off[c + 1] - off[c];
-            if (L < 3 || L > PESTO_CHAINMAP_MAX_LENGTH || (len[grp[c]] && len[grp[c]] != L))
-                return fail(PESTO_ERR_INVALID, "%s: a chain must have 3 to %d slots, as many as every chain of its group", who, PESTO_CHAINMAP_MAX_LENGTH);
-            len[grp[c]] = L;
-            longest = std::max(longest, L);
-            if (++count[grp[c]] > MAX_G) return fail(PESTO_ERR_INVALID, "%s: at most %d chains of a group on a side", who, MAX_G);
-        }
-    }
-    for (int a = 0; a < Cr; ++a)
-        for (int ap = a + 1; ap < Cr; ++ap) { lay.ia.push_back(a); lay.iap.push_back(ap); }
-    for (int b = 0; b < Cm; ++b)
-        for (int bp = b + 1; bp < Cm; ++bp) { lay.ma.push_back(b); lay.map.push_back(bp); }
-    lay.nrb = (longest + RB - 1) / RB;
-    return 0;
+// the pairs c < c' of C chains in ascending order
+void chain_pairs(int C, std::vector<int>& first, std::vector<int>& second) {
+    for (int c = 0; c < C; ++c)
+        for (int cp = c + 1; cp < C; ++cp) { first.push_back(c); second.push_back(cp); }
 }
 
 template <class T> int table(Buffers& bf, const std::vector<T>& v) { return bf.table(v.data(), v.size() * sizeof(T)); }
@@ -491,36 +451,21 @@ int qs_run(const char* who, pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, i
     if (!ref_offsets || !ref_group || !offsets || !group || !xyz_ref || !xyz || !qs_best_out || !qs_global_out || !ics_out || !precision_out || !recall_out ||
         !counts_out || !interface_qs_out || (search && (!mapping_out || !n_mapped_out || !index_out)))
         return fail(PESTO_ERR_INVALID, "bad arguments");
-    if (F < 1 || F > PESTO_CHAINMAP_MAX_FRAMES || Nr < 3 || Nr > 0x3fffffff || Nm < 3 || Nm > 0x3fffffff)
-        return fail(PESTO_ERR_INVALID, "1 to 2^23 frames and 3 <= Nr, Nm < 2^30 residues");
-    if (Cr < 1 || Cr > MAX_C || Cm < 1 || Cm > MAX_C) return fail(PESTO_ERR_INVALID, "1 to %d chains on each side", MAX_C);
+    if (int rc = check_oligomer_sizes(F, Nr, Nm, Cr, Cm, scale)) return rc;
     if (!search && mapping_rows != 1 && mapping_rows != F) return fail(PESTO_ERR_INVALID, "mapping_rows must be 1 or F");
-    if (!(std::isfinite(scale) && scale > 0.0)) return fail(PESTO_ERR_INVALID, "scale must be positive and finite");
     if (!(std::isfinite(contact_thr) && contact_thr > 0.0)) return fail(PESTO_ERR_INVALID, "contact_thr must be positive and finite");
     if (int rc = begin(m, ptr_kind)) return rc;
-    // The four layout arrays live where ptr_kind says, as pesto_chainmap's do. The job lists are made from them on the host, so device
-    // arrays (at most 65 ints each) are brought over first, on the call's stream.
-    std::vector<int32_t> lay_host;
-    if (ptr_kind == PESTO_PTR_DEVICE) {
-        lay_host.resize((size_t)2 * Cr + 2 * Cm + 2);
-        int32_t* h = lay_host.data();
-        const int32_t* src[4] = {ref_offsets, ref_group, offsets, group};
-        const size_t n[4] = {(size_t)Cr + 1, (size_t)Cr, (size_t)Cm + 1, (size_t)Cm};
-        const int32_t* at[4];
-        for (int k = 0; k < 4; ++k) {
-            if (int rc = hip_ok(hipMemcpyAsync(h, src[k], n[k] * 4, hipMemcpyDeviceToHost, (hipStream_t)stream), "copy of the layout to the host failed")) return rc;
-            at[k] = h;
-            h += n[k];
-        }
-        if (int rc = hip_ok(hipStreamSynchronize((hipStream_t)stream), "copy of the layout to the host failed")) return rc;
-        ref_offsets = at[0];
-        ref_group = at[1];
-        offsets = at[2];
-        group = at[3];
-    }
-    Layout lay;
-    if (int rc = check_layout(who, Nr, Nm, Cr, Cm, ref_offsets, ref_group, offsets, group, lay)) return rc;
-    const int nI = (int)lay.ia.size(), nJm = (int)lay.ma.size(), nrb = lay.nrb;
+    // the job lists are made on the host, from the layout as the host holds it
+    OligomerLayout lay;
+    if (int rc = fetch_layout(who, Nr, Nm, Cr, Cm, ref_offsets, ref_group, offsets, group, ptr_kind, stream, lay)) return rc;
+    ref_offsets = lay.ro;
+    ref_group = lay.rg;
+    offsets = lay.mo;
+    group = lay.mg;
+    std::vector<int> ref_a, ref_ap, mod_b, mod_bp;      // the interfaces: the reference's chain pairs; and the model's chain pairs
+    chain_pairs(Cr, ref_a, ref_ap);
+    chain_pairs(Cm, mod_b, mod_bp);
+    const int nI = (int)ref_a.size(), nJm = (int)mod_b.size(), nrb = (lay.longest + RB - 1) / RB;     // (the slot blocks of the longest chain)
     // the two-sided jobs: the mapping's interfaces, or every model chain pair of every interface's groups (the pair (b, b) is no job:
     // its entry is never read)
     std::vector<int> jI, jb, jbp, ibase, mrank(Cm), nmof(Cr), g_nr, g_nm, g_radix, g_ref, g_mod;
@@ -545,8 +490,8 @@ int qs_run(const char* who, pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, i
             return fail(PESTO_ERR_INVALID, "%s: more than 2^20 chain mappings: map the chains with pesto_chainmap and score that mapping with pesto_qsscore", who);
         for (int i = 0; i < nI; ++i) {
             ibase.push_back((int)jI.size());
-            for (int b : mods[ref_group[lay.ia[i]]])
-                for (int bp : mods[ref_group[lay.iap[i]]]) { jI.push_back(i); jb.push_back(b == bp ? -1 : b); jbp.push_back(b == bp ? -1 : bp); }
+            for (int b : mods[ref_group[ref_a[i]]])
+                for (int bp : mods[ref_group[ref_ap[i]]]) { jI.push_back(i); jb.push_back(b == bp ? -1 : b); jbp.push_back(b == bp ? -1 : bp); }
         }
     }
     const int nJ = search ? (int)jI.size() : nI, G = (int)g_nr.size();
@@ -560,7 +505,7 @@ int qs_run(const char* who, pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, i
     const int iMin = search ? -1 : bf.input(mapping_in, (size_t)mapping_rows * Cr * 4);
     const int iRo = bf.table(ref_offsets, (size_t)(Cr + 1) * 4), iRg = bf.table(ref_group, (size_t)Cr * 4), iMo = bf.table(offsets, (size_t)(Cm + 1) * 4),
               iMg = bf.table(group, (size_t)Cm * 4);
-    const int iIa = table(bf, lay.ia), iIap = table(bf, lay.iap), iMa = table(bf, lay.ma), iMap = table(bf, lay.map);
+    const int iIa = table(bf, ref_a), iIap = table(bf, ref_ap), iMa = table(bf, mod_b), iMap = table(bf, mod_bp);
     const int iJI = table(bf, jI), iJb = table(bf, jb), iJbp = table(bf, jbp), iIb = table(bf, ibase), iMr = table(bf, mrank), iNo = table(bf, nmof);
     const int iGr = table(bf, g_nr), iGm = table(bf, g_nm), iGx = table(bf, g_radix), iGf = table(bf, g_ref), iGd = table(bf, g_mod);
     const int iMp = search ? bf.output(mapping_out, (size_t)F * Cr * 4) : -1, iNm = search ? bf.output(n_mapped_out, (size_t)F * 4) : -1,
@@ -605,7 +550,7 @@ int qs_run(const char* who, pesto_model* m, int64_t F, int64_t Nr, int64_t Nm, i
         for (int64_t f0 = 0; f0 < F; f0 += chunk) {
             const unsigned nf = (unsigned)std::min(chunk, F - f0);
             const float* X = bf.ptr<const float>(iX) + (size_t)f0 * Nm * 3;
-            hipLaunchKernelGGL(k_qs_frames, dim3(nf), dim3(NT), 0, bf.stm, (int)Nm, X, rbad, st, bf.ptr<int>(iBad));
+            hipLaunchKernelGGL(k_oligomer_frames, dim3(nf), dim3(OLIGOMER_NT), 0, bf.stm, (int)Nm, X, rbad, bf.ptr<int>(iBad));
             if (nJm > 0) {
                 hipLaunchKernelGGL(k_qs_tile<false>, dim3((unsigned)(nJm * nrb), nf), dim3(NT), 0, bf.stm, nrb, (int)Cr, 0, 0ll, mo, mo, bf.ptr<const int>(iMa),
                                    bf.ptr<const int>(iMap), (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, X, X,

@@ -60,8 +60,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from .chainmap import MAX_FRAMES, _chains, _positive
-from .docking import _frames
+from .chainmap import _oligomer, _positive
 from .trajectory import _model_of
 
 MAX_MAPPINGS = 2 ** 20          # PESTO_QSSCORE_MAX_MAPPINGS
@@ -115,32 +114,9 @@ def mapping_of_index(index, ref_group, group):
 
 def _layout(xyz_ref, ref_offsets, ref_group, xyz, offsets, group, contact_thr, scale):
     """the checked arguments both entry points share: (y, x, F, Nr, Nm, ro, rg, mo, mg, contact_thr, scale)"""
-    y = _frames(xyz_ref, "xyz_ref")
-    if int(y.shape[0]) != 1:
-        raise ValueError(f"xyz_ref must be the one reference, [Nr, 3] or [1, Nr, 3], got {int(y.shape[0])} frames")
-    x = _frames(xyz, "xyz")
-    F, Nr, Nm = int(x.shape[0]), int(y.shape[1]), int(x.shape[1])
-    if not 1 <= F <= MAX_FRAMES or Nr >= 2 ** 30 or Nm >= 2 ** 30:
-        raise ValueError(f"1 to 2**23 frames and fewer than 2**30 residues on each side, got {F} frames, {Nr} and {Nm} residues")
-    ro, rg = _chains(ref_offsets, ref_group, Nr, "ref_")
-    mo, mg = _chains(offsets, group, Nm, "")
-    # the groups' ids, numbered densely over both sides (the library takes ids below 128)
-    ids = np.unique(np.concatenate([rg, mg]), return_inverse=True)[1].astype(np.int32)
-    rg, mg = np.ascontiguousarray(ids[:rg.size]), np.ascontiguousarray(ids[rg.size:])
-    length = {}
-    for g, L in zip(np.concatenate([rg, mg]), np.concatenate([np.diff(ro), np.diff(mo)])):
-        if length.setdefault(int(g), int(L)) != int(L):
-            raise ValueError(f"all chains of a group share its slots: a chain of {int(L)} slots in a group of {length[int(g)]}")
+    lay = _oligomer(xyz_ref, ref_offsets, ref_group, xyz, offsets, group)
     sc = _positive(scale, "scale", 10.0)
-    thr = _positive(contact_thr, "contact_thr", 8.0)
-    if _lib.is_torch(y):
-        import torch
-        infinite = bool(torch.isinf(y).any())
-    else:
-        infinite = bool(np.isinf(y).any())
-    if infinite:
-        raise ValueError("xyz_ref: a coordinate of the reference is infinite (a missing residue is NaN)")
-    return y, x, F, Nr, Nm, ro, rg, mo, mg, thr, sc
+    return (*lay, _positive(contact_thr, "contact_thr", 8.0), sc)
 
 
 def _check_mapping(m, rg, mg):

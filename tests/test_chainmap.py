@@ -253,27 +253,35 @@ def test_refused_calls_write_nothing_and_the_next_call_is_served(on_device):
     with pytest.raises(ValueError, match="n_iter"):
         C.chain_map(put(s["xyz_ref"]), s["ro"], s["rg"], put(s["xyz"]), s["mo"], s["mg"], n_iter=0)
     assert same_result(run(s, on_device), good)
-    # the device's verdict, through the C ABI (the Python layer refuses these first)
+    # the library's own refusals, through the C ABI (the Python layer refuses these first)
     model, lib = _default_model(0), _lib.load()
     y, x = put(s["xyz_ref"]), put(s["xyz"])
     side = _lib.Side(x, model._gpu)
-    outs = [put(np.full(n, 7, t)) for n, t in ((1, np.float32), (2, np.int32), (2, np.float32), (1, np.int32), (1, np.int32), (1, np.int32),
-                                                (9, np.float64), (3, np.float64))]
 
-    def call(ro, rg, mo, mg):
+    def sentinels(Cr):
+        return [put(np.full(n, 7, t)) for n, t in ((1, np.float32), (Cr, np.int32), (Cr, np.float32), (1, np.int32), (1, np.int32), (1, np.int32),
+                                                    (9, np.float64), (3, np.float64))]
+    outs = sentinels(2)
+
+    def call(ro, rg, mo, mg, y=y, x=x, outs=outs):
         arrays = [put(np.asarray(v, np.int32)) for v in (ro, rg, mo, mg)]
-        return lib.pesto_chainmap(model.handle, 1, 16, 16, 2, 2, *(side.ptr(v) for v in arrays), side.ptr(y), side.ptr(x), 16.0, 0.5, 5, 1.0,
-                                  *(side.ptr(v) for v in outs), side.kind, side.stream)
+        return lib.pesto_chainmap(model.handle, 1, int(y.shape[0]), int(x.shape[1]), len(rg), len(mg), *(side.ptr(v) for v in arrays), side.ptr(y),
+                                  side.ptr(x), 16.0, 0.5, 5, 1.0, *(side.ptr(v) for v in outs), side.kind, side.stream)
 
-    def refused(rc, text):
+    def refused(rc, text, arrays=outs):
         assert rc == -1
         with pytest.raises(_lib.PestoError) as e:
             _lib.check(rc, lib.pesto_chainmap_last_error)
         assert str(e.value) == "libpesto_hip error -1: chainmap: " + text
-        assert all((host(v) == 7).all() for v in outs)
+        assert all((host(v) == 7).all() for v in arrays)
     refused(call(s["ro"], s["rg"], [0, 16, 8], s["mg"]), "offsets must start at 0, end at the number of residues and ascend")
     refused(call([0, 9, 16], s["rg"], s["mo"], s["mg"]), "a chain must have 3 to 4096 slots, as many as every chain of its group")
     refused(call(s["ro"], [0, 128], s["mo"], s["mg"]), "group ids must lie in [0, 128)")
+    # 13 chains of one group on the reference side
+    bouts = sentinels(13)
+    refused(call(big["ro"], big["rg"], big["mo"], big["mg"], put(big["xyz_ref"]), put(big["xyz"]), bouts), "at most 12 chains of a group on a side", bouts)
+    # a group that only the model has, with chains of 3 and 4 slots: all chains of a group, on both sides, share its slots
+    refused(call(s["ro"], s["rg"], [0, 8, 11, 15], [0, 1, 1], x=put(s["xyz"][:, :15])), "a chain must have 3 to 4096 slots, as many as every chain of its group")
     assert call(s["ro"], s["rg"], s["mo"], s["mg"]) == 0
     want = C.chain_map(y, s["ro"], s["rg"], x, s["mo"], s["mg"], norm_len=16.0, d0=0.5, scale=1.0)
     assert all(same_bits(host(a).reshape(-1), host(b).reshape(-1)) for a, b in zip(outs, want))

@@ -363,6 +363,14 @@ def test_refused_calls_write_nothing_and_the_next_call_is_served(on_device):
     rc = lib.pesto_qsmap(model.handle, 1, 30, 30, 10, 10, *(side.ptr(v) for v in lay), side.ptr(yb), side.ptr(xb), THR, SCALE, *(side.ptr(v) for v in bouts),
                          side.kind, side.stream)
     refused(rc, "qsmap: more than 2^20 chain mappings: map the chains with pesto_chainmap and score that mapping with pesto_qsscore", bouts)
+    # 13 chains of one group on the reference side
+    huge = make_qs_system(2, [(3, 13, 1)], n_nan=0)
+    lay = [put(i32(huge[k])) for k in ("ro", "rg", "mo", "mg")]
+    yh, xh = put(huge["xyz_ref"]), put(huge["xyz"])
+    houts = [put(np.full(n, 7, t)) for n, t in ((13, np.int32), (1, np.int32), (1, np.int64)) + ((1, np.float32),) * 5 + ((3, np.int32), (169, np.float32))]
+    rc = lib.pesto_qsmap(model.handle, 1, 39, 3, 13, 1, *(side.ptr(v) for v in lay), side.ptr(yh), side.ptr(xh), THR, SCALE, *(side.ptr(v) for v in houts),
+                         side.kind, side.stream)
+    refused(rc, "qsmap: at most 12 chains of a group on a side", houts)
     # and the next calls are served, with the Python layer's bits
     assert call(s["ro"], s["rg"], s["mo"], s["mg"], planted) == 0
     assert all(same_bits(host(a).reshape(-1), host(b).reshape(-1)) for a, b in zip(outs, good))
